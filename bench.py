@@ -6,10 +6,13 @@ instances (10 slots), batch 4 PER GPU, bf16 autocast, one full training step = f
 gradient-norm clip + AdamW update (+ DDP gradient all-reduce over RCCL when N > 1; weak scaling: per-GPU work fixed).
 Synthetic data / deterministic random-init weights (maggie_amd.utils.synth): no dataset or checkpoint is reachable offline.
 
-Prints ONE JSON line on rank 0. `value` = whole-job instance-frames/s with the batch already resident in HBM.
+Prints ONE JSON line on rank 0. `value` = whole-job instance-frames/s with the batch already resident in HBM;
+`ms_per_step` = wall milliseconds of one timed step. A plain run only sets up, warms up, times --steps steps, writes
+--dump-outputs and prints the line. With --full it also measures and checks what the headline figure does not need:
 `roofline` = the dominant kernel family (implicit-GEMM MFMA conv kernels), measured live with HIP events on extra
 instrumented steps of the same workload; `cpu_baseline` = the CPU oracle (oracle/refmodel.py, a port, never the product)
-timed on this host's cores on a bounded sample (rank 0, N = 1 only).
+timed on this host's cores on a bounded sample, and `accuracy` = BASELINE configs[0] through the HIP path against the
+CPU oracle (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -44,18 +47,25 @@ def parse():
                          "the realistic ratio, drifting as AdamW trains)")
     ap.add_argument('--iter', type=int, default=None, help="batch['iter'] (default: 100 for --workload gt, 10000 for pred)")
     ap.add_argument('--edge', type=float, default=40.0, help='soft-edge width (px at 512) of the synthetic alphas: 40 -> active ratio ~0.15 with --workload gt')
-    ap.add_argument('--no-trace', action='store_true', help='skip the rocprofv3 kernel trace of the graph-replayed steps (roofline.graph_replay)')
-    ap.add_argument('--cpu-baseline-full', action='store_true', help='cpu_baseline with 2 warm-ups + 5 timed steps per leg (several minutes)')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the roofline pass (instrumented eager steps + a rocprofv3 kernel-trace '
+                         'child run), the CPU oracle baseline and the accuracy leg against the CPU oracle (minutes). Off by default')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help='after the timed steps write what the last one computed -- the model outputs, the loss terms and the parameters after the '
+                         'optimizer update -- as DIR/<name>.npy (float32; an array of more than %d elements as that many values at fixed, seeded '
+                         'positions: numpy default_rng(0).choice over its flat index, sorted)' % DUMP_SAMPLE)
+    ap.add_argument('--no-trace', action='store_true', help='--full: skip the rocprofv3 kernel trace of the graph-replayed steps (roofline.graph_replay)')
+    ap.add_argument('--cpu-baseline-full', action='store_true', help='--full: cpu_baseline with 2 warm-ups + 9 timed steps per leg (several minutes)')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32', 'fp16'],
                     help="fp16 = the reference's --precision 16 recipe: fp16 autocast + GradScaler (engine/train.py:208,227-229,265-281)")
     ap.add_argument('--sync-bn', action='store_true', help='nn.SyncBatchNorm like configs/maggie_image.yaml:33 (N > 1)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the cpu_baseline and accuracy legs')
+    ap.add_argument('--no-roofline', action='store_true', help='--full: skip the roofline pass')
     ap.add_argument('--cpu-baseline-worker', action='store_true', help=argparse.SUPPRESS)
-    ap.add_argument('--cpu-threads', type=int, default=0, help='cpu_baseline: torch threads (0 = try 32 and all host cores, report the faster)')
+    ap.add_argument('--cpu-threads', type=int, default=0, help='--full: cpu_baseline torch threads (0 = try 32 and all host cores, report the faster)')
     ap.add_argument('--acc-file', default='', help=argparse.SUPPRESS)
     ap.add_argument('--dry-run', action='store_true', help=argparse.SUPPRESS)     # rank plumbing only (tests): rendezvous, count the ranks, print, no model
-    ap.add_argument('--layers', action='store_true', help='print the per-shape conv kernel table to stderr')
+    ap.add_argument('--layers', action='store_true', help='--full: print the per-shape conv kernel table of the roofline pass to stderr')
     ap.add_argument('--ddp', action='store_true', help='all-reduce gradients with torch DistributedDataParallel (like the reference) instead of '
                                                       'maggie_amd.parallel.GradSync (flat-buffer RCCL all-reduce, the default for N > 1)')
     ap.add_argument('--optimizer', default='flat', choices=['flat', 'fused', 'foreach'],
@@ -202,6 +212,8 @@ def main():
             host_t.append([1e3 * (t[i + 1] - t[i]) for i in range(3)])
         stats['active_px'] = out['detail_mask']
         stats['loss'] = loss['total']
+        if args.dump_outputs:
+            stats['last'] = (out, loss)
         # per-step active ratio: only a reference to the step's own mask is kept here (outputs of a replayed step are private copies);
         # the reductions run after the timed region
         hist = stats.setdefault('active_masks', [])
@@ -243,6 +255,8 @@ def main():
     sync()
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0)
     step_ms = [marks[i_].elapsed_time(marks[i_ + 1]) for i_ in range(args.steps)]
+    if args.dump_outputs and rank == 0:                       # before --full's instrumented steps move the model on
+        dump_outputs(args.dump_outputs, *stats['last'], params)
 
     if host_t and rank == 0:
         sys.stderr.write('host ms/step (forward+loss, backward, clip+AdamW): %s\n' % np.round(np.mean(host_t[-args.steps:], 0), 2).tolist())
@@ -255,7 +269,7 @@ def main():
     loss_val = float(stats['loss'].item())
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (1) live HIP events: per-launch timing needs every conv launched individually, so two extra instrumented steps run eagerly (the
         #     timed steps above replay the same kernels, same launch configurations, back to back from hipGraphs);
         # (2) the graph-replayed steps themselves: a rocprofv3 --kernel-trace child of this same command (fewer steps) gives the average
@@ -341,7 +355,7 @@ def main():
 
     cpu_baseline = None
     accuracy = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # BASELINE.json's metric also names "alpha max-abs err vs CPU": configs[0] (maggie_image.yaml, 1 instance, 1 x 256 x 256, batch 1, fp32 eval
         # forward) through the HIP path here, through the CPU oracle in the child below, compared there (the oracle is the checker, never the product)
         acc_file = hip_accuracy_outputs(dev)
@@ -361,7 +375,7 @@ def main():
                                    'slowest_steps': sorted(((round(v, 2), i) for i, v in enumerate(step_ms)), reverse=True)[:3],
                                    'note': 'device time between per-step events of the timed region (rank 0)'},
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': args.dtype, 'data': 'synthetic',
+            'dtype': args.dtype, 'data': 'synthetic', 'full': args.full,
             'per_gpu': round(value / world, 3),
             'config': {'workload': 'maggie_%s.yaml train step: %dx%d, %d instances (10 slots), batch %d frames/GPU x %d frame(s), iter=%d (%s), '
                                    'fwd+loss+bwd+clip+AdamW' % (kind, args.size, args.size, args.instances, b, n_f, args.iter,
@@ -405,6 +419,33 @@ def gather_device_ids(local_rank, world):
     out = [None] * world
     dist.all_gather_object(out, int(torch.cuda.current_device()))
     return out
+
+
+DUMP_SAMPLE = 1 << 20                 # --dump-outputs: elements kept of a larger array (4 MB in float32)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_array(t):
+    """A tensor as float32 numpy: whole, or DUMP_SAMPLE of its elements at fixed seeded flat positions (sorted) when it is larger."""
+    t = t.detach()
+    if t.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, out, loss, params):
+    """--dump-outputs: what one training step hands its caller -- the output dict, the loss terms and the parameters after the optimizer
+    update (all trainable parameters flattened in model.parameters() order, as one array) -- as out_dir/<name>.npy."""
+    arrays = {k: dump_array(v) for k, v in out.items()}
+    arrays.update({(k if k.startswith('loss') else 'loss_' + k): dump_array(v) for k, v in loss.items() if torch.is_tensor(v)})
+    arrays['params'] = dump_array(torch.cat([p.detach().reshape(-1).float() for p in params]))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes, more than %d' % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in sorted(arrays.items()):
+        np.save(os.path.join(out_dir, k + '.npy'), a)
 
 
 def spawn_ranks(n):

@@ -527,3 +527,35 @@ def test_bench_two_ranks_time_slicing_one_gpu_stay_finite():
         assert line, out[-2000:]
         r = json.loads(line[-1])
         assert r['n_gpus'] == 2 and np.isfinite(r['value']) and r['value'] > 0, r
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` as the driver runs it: ONE line with `steps` = K and `ms_per_step`, none of --full's
+    legs (roofline, cpu_baseline, accuracy), and the last timed step's outputs, loss terms and parameters as finite float32 arrays, 64 MB at most."""
+    import json
+    import os
+    import subprocess
+    import sys
+    _dev()
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    env.pop('MAGGIE_SPARSE_CAPACITY', None)                      # the product default, as the driver runs it
+    p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr.decode(errors='replace')[-3000:]
+    line = [l for l in p.stdout.decode(errors='replace').splitlines() if l.startswith('{"metric"')]
+    assert len(line) == 1, p.stdout.decode(errors='replace')[-2000:]
+    r = json.loads(line[0])
+    assert r['steps'] == 3 and r['warmup'] == 1 and r['ms_per_step'] > 0 and np.isfinite(r['value']) and r['value'] > 0, r
+    assert r['full'] is False and r['roofline'] is None and r['cpu_baseline'] is None and r['accuracy'] is None
+    names = sorted(os.listdir(str(tmp_path)))
+    for n in ('alpha_os1.npy', 'alpha_os4.npy', 'alpha_os8.npy', 'refined_masks.npy', 'detail_mask.npy', 'loss_total.npy', 'params.npy'):
+        assert n in names, names
+    total = 0
+    for n in names:
+        a = np.load(str(tmp_path / n))
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(str(tmp_path / 'loss_total.npy'))) == pytest.approx(r['config']['loss_total'], abs=1e-4)

@@ -685,3 +685,29 @@ def test_bench_gpus_flag_spawns_one_rank_per_gpu():
     res = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--dry-run'], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          env=dict(env, WORLD_SIZE='1', RANK='0'), timeout=300)
     assert res.returncode != 0 and b'--gpus 2 but WORLD_SIZE=1' in res.stderr
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per output / loss term plus the flattened parameters; an array larger than bench.DUMP_SAMPLE
+    is written as that many values at fixed seeded positions (the same on every call, in flat-index order); everything within 64 MB."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(3 * bench.DUMP_SAMPLE, dtype=torch.float32).reshape(3, bench.DUMP_SAMPLE)
+    out = {'alpha_os1': big, 'detail_mask': big.remainder(7) == 0}
+    loss = {'total': torch.tensor(1.5, requires_grad=True) * 2, 'loss_rec_os1': torch.tensor(0.25)}
+    params = [torch.nn.Parameter(torch.ones(3, 4)), torch.nn.Parameter(torch.zeros(5))]
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), out, loss, params)
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == ['alpha_os1.npy', 'detail_mask.npy', 'loss_rec_os1.npy', 'loss_total.npy', 'params.npy']
+    arrs = {n[:-4]: np.load(str(tmp_path / 'a' / n)) for n in names}
+    for n in names:
+        assert arrs[n[:-4]].dtype == np.float32, n
+        assert np.array_equal(arrs[n[:-4]], np.load(str(tmp_path / 'b' / n))), n
+    a = arrs['alpha_os1']
+    assert a.shape == (bench.DUMP_SAMPLE,) and np.all(np.diff(a) > 0) and a[-1] >= bench.DUMP_SAMPLE    # distinct sorted positions over all rows
+    assert np.array_equal(arrs['detail_mask'], (a % 7 == 0).astype(np.float32))                        # the same positions in every array
+    assert float(arrs['loss_total']) == 3.0 and float(arrs['loss_rec_os1']) == 0.25
+    assert np.array_equal(arrs['params'], np.array([1.0] * 12 + [0.0] * 5, np.float32))
+    assert sum(x.nbytes for x in arrs.values()) <= bench.DUMP_MAX_BYTES

@@ -11,6 +11,16 @@ from maggie_amd.utils import synth
 from oracle import refmodel
 
 
+@pytest.fixture(autouse=True)
+def _golden_thread_count():
+    """torch's CPU kernels split fp32 sums by thread count, and the fixtures were produced with 8 threads: with 1 to 6 the oracle drifts past
+    the bars below on some entries. The count is pinned so that the outcome does not depend on how many cores the host has."""
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(n)
+
+
 def _close(a, b, tol):
     return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max()) <= tol
 

@@ -535,6 +535,30 @@ int mg_postprocess_alpha(const float* in, int P, int Hin, int Win, int crop_h, i
                          void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Connected components of many 2-D binary planes (csrc/ccl.hip): tile union-find in LDS, border merge, flatten. The root of a component
+ * is its smallest row-major index, so every result is independent of scheduling. H * W < 2^31 (else -2); every scratch buffer comes
+ * from the caller, sized by mg_cc_scratch_bytes(op, P, H, W, &bytes) for op MG_CC_OP_LABEL / _CONN / _LARGEST. No host synchronisation.
+ *   mg_cc_label              : mask u8 [P][H][W] (non-zero = foreground), connectivity 1 (4-neighbours) or 2 (8-neighbours) ->
+ *                              labels i32 [P][H][W] = 1..num[p] in the raster order of each component's first pixel, background 0:
+ *                              skimage.measure.label's array; num i32 [P].
+ *   mg_metric_conn           : out f64 [P] = per plane conn_diff of maggie/utils/metric.py:240-298 (before * 0.001): levels i = 1..10,
+ *                              t_i = float32(i * 0.1), intersection_i = (gt >= t_i) & (pred >= t_i) compared in fp32 (numpy < 2),
+ *                              largest 4-connected component (ties: the smallest root); round_down = t_{i-1} for the first level whose
+ *                              largest component misses the pixel, else 1; term |(1 - gd [gd >= 0.15]) - (1 - pd [pd >= 0.15])| m in
+ *                              fp32, summed in fp64 in a fixed order (bit-reproducible). mask_mode as for the metrics above.
+ *   mg_postprocess_largest_cc: out = alpha * [pixel in the largest 8-connected component of alpha > thresh] (maggie/utils/postprocessing.py
+ *                              :66-86; ties: the smallest root); a plane with no foreground is copied unchanged. Capturable in a graph.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_CC_OP_LABEL 0
+#define MG_CC_OP_CONN 1
+#define MG_CC_OP_LARGEST 2
+int mg_cc_scratch_bytes(int op, int P, int H, int W, long* bytes);
+int mg_cc_label(const uint8_t* mask, int P, int H, int W, int connectivity, int32_t* labels, int32_t* num, void* scratch, void* stream);
+int mg_metric_conn(const float* pred, const float* gt, const float* trimap, int mask_mode, int P, int H, int W, void* scratch, double* out,
+                   void* stream);
+int mg_postprocess_largest_cc(const float* alpha, int P, int H, int W, float thresh, void* scratch, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Sparse refinement head with a DEVICE row count (round 2).
  * The reference's detail stage (maggie/network/decoder/resnet_inst_matt_spconv.py:196-270) sizes every spconv feature matrix from
  * `torch.nonzero` (:206) -- a device->host read per forward, after which ~430 small launches are paced by the host. Here the site

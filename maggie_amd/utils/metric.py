@@ -7,12 +7,15 @@ model's output tensors where they are instead of numpy copies:
 `pred`, `gt`, `trimap`: fp32 device tensors (N, *, H, W) ((T, N_i, H, W) or (B, T, N_i, H, W) for dtSSD). A call costs one pass over
 the planes (HIP kernels mg_metric_plane_sums / mg_metric_grad / mg_metric_dtssd) and one small device->host read of fp64 sums; the
 reference copies every plane to the host, reduces in numpy and, for Grad, ships the planes back to the GPU.
-Conn and MESSDdt (connected components / optical-flow warping on the CPU: skimage, cv2) stay with the caller, as SURVEY 8f says."""
+Conn (:224-300; mg_metric_conn: the largest 4-connected component at each of the 10 threshold levels, csrc/ccl.hip) is built by
+build_metric(..., device_conn=True); by default it stays with the caller.
+MESSDdt (optical-flow warping on the CPU: cv2) stays with the caller, as SURVEY 8f says."""
 import numpy as np
 import torch
 
 from .. import hip
 from ..hip import c_int, c_long
+from . import connected
 
 
 def _planes(x):
@@ -128,12 +131,27 @@ class dtSSD(Metric):
         return err / (N + 1e-10)
 
 
+class Conn(Metric):
+    """Connectivity error (metric.py:224-300): per plane, the largest 4-connected component of (gt >= t) & (pred >= t) at t = 0.1 .. 1.0
+    gives each pixel its round-down level; score = sum of conn_diff * 0.001, count = number of planes."""
+
+    def compute_metric(self, pred, gt, tri, mode, **kargs):
+        P, H, W = pred.shape
+        out = torch.empty(P, dtype=torch.float64, device=pred.device)
+        ws = connected.scratch(connected.OP_CONN, P, H, W, pred.device)
+        hip.call('mg_metric_conn', hip.ptr(pred), hip.ptr(gt), hip.ptr(tri), c_int(mode), c_int(P), c_int(H), c_int(W), hip.ptr(ws),
+                 hip.ptr(out), hip.stream())
+        return float(out.sum()) * 0.001, P
+
+
 _DEVICE_METRICS = {'SAD': SAD, 'MSE': MSE, 'MAD': MAD, 'Grad': Grad, 'dtSSD': dtSSD}
 
 
-def build_metric(metrics):
-    """{name: metric object} like metric.py:534-538, for the metrics that live on the device."""
-    missing = [m for m in metrics if m not in _DEVICE_METRICS]
+def build_metric(metrics, device_conn=False):
+    """{name: metric object} like metric.py:534-538, for the metrics that live on the device. 'Conn' is built on the device only with
+    device_conn=True; without it (and for 'MESSDdt' always) a host-side metric raises NotImplementedError."""
+    known = dict(_DEVICE_METRICS, Conn=Conn) if device_conn else _DEVICE_METRICS
+    missing = [m for m in metrics if m not in known]
     if missing:
         raise NotImplementedError('host-side metrics (skimage / cv2) are not part of this build: %s' % missing)
-    return {m: _DEVICE_METRICS[m]() for m in metrics}
+    return {m: known[m]() for m in metrics}

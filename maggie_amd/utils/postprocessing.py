@@ -2,11 +2,15 @@
 fuses the alpha snapping the reference's eval loops apply afterwards on the host (maggie/engine/test.py:139-142,229-231).
 
 `transform_info` is the list the reference's dataloader attaches to a batch: dicts with name 'resize' (`ori_size`) / 'padding'
-(`pad_size`), applied in that order on the way in and undone in reverse here. One HIP kernel (mg_postprocess_alpha) per resize."""
+(`pad_size`), applied in that order on the way in and undone in reverse here. One HIP kernel (mg_postprocess_alpha) per resize.
+
+`postprocess` mirrors maggie/utils/postprocessing.py:66-86: keep only the largest 8-connected component of alpha > thresh
+(mg_postprocess_largest_cc, csrc/ccl.hip), decided on the device."""
 import torch
 
 from .. import hip
-from ..hip import c_int
+from ..hip import c_int, c_float
+from . import connected
 
 
 def _scalar(v):
@@ -48,3 +52,21 @@ def reverse_transform_tensor(img, transform_info, snap=False):
         x = _run(x, crop_h, crop_w, crop_h, crop_w, snap and not snapped)      # pending crop and/or snapping (exact copy: scale 1)
     shape[-2:] = crop_h, crop_w
     return x.reshape(shape)
+
+
+def postprocess(alpha, thresh=0.05):
+    """alpha: (..., H, W) device tensor -> fp32 of the same shape: per plane, alpha * [pixel in the largest 8-connected component of
+    alpha > thresh] (a tie goes to the component whose first pixel comes first in raster order); a plane without foreground is returned
+    unchanged. No host synchronisation: capturable in a graph."""
+    hip.need_cuda(alpha)
+    if alpha.dim() < 2:
+        raise hip.MaggieHipError('postprocess needs (..., H, W) planes (got shape %s)' % (tuple(alpha.shape),))
+    shape = tuple(alpha.shape)
+    H, W = shape[-2:]
+    x = alpha.reshape(-1, H, W).float().contiguous()
+    P = x.shape[0]
+    out = torch.empty_like(x)
+    if x.numel() > 0:
+        ws = connected.scratch(connected.OP_LARGEST, P, H, W, x.device)
+        hip.call('mg_postprocess_largest_cc', hip.ptr(x), c_int(P), c_int(H), c_int(W), c_float(thresh), hip.ptr(ws), hip.ptr(out), hip.stream())
+    return out.reshape(shape)

@@ -512,6 +512,38 @@ int mg_preprocess_planes(const uint8_t* in, float* out, const int32_t* src_of_sl
                          int Ho, int Wo, int thresh, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Ground-truth maps of the datasets on the device (csrc/morph.hip): grey-scale morphology with OpenCV's ellipse, on uint8 planes.
+ *   E = getStructuringElement(MORPH_ELLIPSE, (k, k)), anchor a = k / 2; dilate: dst[y][x] = max over E[i][j] != 0 of src[y+i-a][x+j-a],
+ *   erode: the same offsets with min; pixels outside the image take no part; n iterations = the filter applied n times. All n passes
+ *   of a 64 x 64 tile run out of LDS in one launch (halo n*(k/2) up / left, n*(k-1-k/2) down / right): one read of the input, one write
+ *   of the product. Integer work: bit-exact, deterministic, no host synchronisation (capturable once mg_morph_prepare has run).
+ *   kn: DEVICE int32 [frames][2] = (k, n) of every frame, 1 <= k <= 31, n >= 1. halo_max: the caller's bound on n * (k - 1) over the
+ *   frames, 0 <= halo_max <= MG_MORPH_MAX_HALO (else -2); it sizes the LDS tile, and a frame whose table entry exceeds it is computed
+ *   with k and then n clamped to the bound (never out of bounds).
+ *   mg_morph_prepare   : uploads the ellipse span table to the current device (implicit in the first call of the entries below; call it
+ *                        before capturing a graph).
+ *   mg_morph_u8        : in u8 [planes][H][W] -> dil, ero u8 [planes][H][W] (either may be NULL); frame of a plane = plane / planes_per_frame.
+ *   mg_transition_gt   : in u8 [frames][n_in][H][W] -> out fp32 [frames][n_slots][H][W]; slot s of frame f shows plane src_of_slot[f*n_slots+s]
+ *                        (device int32; < 0 = empty slot -> zeros; NULL = identity, n_slots == n_in); values below `thresh` read as 0
+ *                        (transforms.py:744). MG_GT_TRANSITION: [dilate > erode] (gen_transition_gt, maggie/dataloader/utils.py:15-35, as
+ *                        called by him.py:185-189: its `masks` branch is dead there). MG_GT_TRIMAP: 2 where v >= 128, then 1 where
+ *                        dilate > erode, else 0 (him.py:190-196, vim.py:198-203).
+ *   mg_diff_transition : in u8 [T][n_in][H][W] -> out fp32 [T][n_slots][H][W] (vim.py:171-183,211): frame 0 all ones; frame t >= 1 =
+ *                        [n-pass dilation of the union over instances of (|a_t - a_{t-1}| > diff_thresh)] written to every slot; values
+ *                        below `thresh` read as 0. kn entry 0 is not read.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_MORPH_MAX_HALO 48
+#define MG_GT_TRANSITION 0
+#define MG_GT_TRIMAP 1
+int mg_morph_prepare(void);
+int mg_morph_u8(const uint8_t* in, uint8_t* dil, uint8_t* ero, const int32_t* kn, int halo_max, long planes, int planes_per_frame, int H, int W,
+                void* stream);
+int mg_transition_gt(const uint8_t* in, float* out, const int32_t* src_of_slot, const int32_t* kn, int halo_max, int frames, int n_in,
+                     int n_slots, int H, int W, int thresh, int mode, void* stream);
+int mg_diff_transition(const uint8_t* in, float* out, const int32_t* kn, int halo_max, int T, int n_in, int n_slots, int H, int W, int thresh,
+                       int diff_thresh, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

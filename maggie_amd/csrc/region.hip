@@ -8,48 +8,12 @@
 // is reading the four site counts to size the feature matrices.
 #include "common.h"
 #include "../../include/maggie_hip.h"
+#include "se_table.h"
 #include <math.h>
-#include <mutex>
 
 namespace {
 
 typedef unsigned long long u64;
-constexpr int MAXK = 32;
-
-// ---- OpenCV getStructuringElement(MORPH_ELLIPSE,(k,k)) row spans, relative to the anchor k/2 -----------------------
-struct SeTable { int8_t lo[MAXK][MAXK]; int8_t hi[MAXK][MAXK]; };   // [k][row]; lo > hi => empty row
-__constant__ SeTable c_se;
-std::once_flag g_se_once;
-int g_se_rc = 0;
-
-void build_se_table(SeTable& t) {
-    for (int k = 0; k < MAXK; ++k)
-        for (int i = 0; i < MAXK; ++i) { t.lo[k][i] = 1; t.hi[k][i] = 0; }
-    for (int k = 1; k < MAXK; ++k) {
-        if (k == 1) { t.lo[1][0] = 0; t.hi[1][0] = 0; continue; }
-        int r = k / 2, c = k / 2;
-        double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
-        for (int i = 0; i < k; ++i) {
-            int dy = i - r;
-            if (abs(dy) <= r) {
-                int dx = (int)nearbyint(c * sqrt((r * r - dy * dy) * inv_r2));   // cvRound: round half to even
-                int j1 = c - dx < 0 ? 0 : c - dx;
-                int j2 = c + dx + 1 > k ? k : c + dx + 1;
-                if (j2 > j1) { t.lo[k][i] = (int8_t)(j1 - c); t.hi[k][i] = (int8_t)(j2 - 1 - c); }
-            }
-        }
-    }
-}
-
-int ensure_se_table() {
-    std::call_once(g_se_once, [] {
-        SeTable t;
-        build_se_table(t);
-        hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_se), &t, sizeof(t));
-        g_se_rc = (int)e;
-    });
-    return g_se_rc;
-}
 
 // ---- pack ------------------------------------------------------------------------------------------------------------
 // mode 0: lo < a < hi ; mode 1: a > 0.  One wave packs one 64-pixel word with a ballot (coalesced 256-byte reads).

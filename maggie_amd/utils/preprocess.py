@@ -83,7 +83,10 @@ class DevicePreprocessor:
     def __init__(self, max_inst=10, downscale_mask=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
         self.max_inst, self.downscale_mask, self.mean, self.std, self.device = max_inst, downscale_mask, mean, std, device
 
-    def __call__(self, frames_u8, alphas_u8=None, masks_u8=None, slot_ids=None):
+    def __call__(self, frames_u8, alphas_u8=None, masks_u8=None, slot_ids=None, *, transition=None, trimap=False):
+        """`transition=(k_size, iterations)` adds the training entry 'transition' from the alphas (utils/groundtruth.py): one frame -> the
+        per-instance band of him.py:185-189 in the same slots as 'alpha'; a clip (T > 1) -> the frame-difference rule of vim.py:171-183.
+        `trimap=True` adds the evaluation entry 'trimap' (him.py:190-196) from the alphas as given (`ori_alphas`: no `< 5` rule)."""
         out = {'image': normalize_frames(frames_u8, self.mean, self.std, self.device)}
         T, _, H, W = out['image'].shape
         n_slots = self.max_inst if slot_ids is not None else None
@@ -94,4 +97,17 @@ class DevicePreprocessor:
             m = masks_u8.reshape(T, -1, H, W)
             size = (H // 8, W // 8) if self.downscale_mask else None                                   # him.py:172-173
             out['mask'] = scale_planes(m, n_slots, slot_ids, size, 0, self.device)
+        if transition is not None or trimap:
+            from . import groundtruth
+            if alphas_u8 is None:
+                raise ValueError('transition / trimap are made from the alphas: alphas_u8 is missing')
+            a = alphas_u8.reshape(T, -1, H, W)
+            if transition is not None:
+                k_size, iterations = transition
+                if T == 1:
+                    out['transition'] = groundtruth.transition_gt(a, k_size, iterations, 5, n_slots, slot_ids, self.device)
+                else:
+                    out['transition'] = groundtruth.diff_transition(a, k_size, iterations, 5, n_slots, device=self.device)
+            if trimap:
+                out['trimap'] = groundtruth.trimap(a, self.device)
         return out

@@ -544,6 +544,48 @@ int mg_diff_transition(const uint8_t* in, float* out, const int32_t* kn, int hal
                        int diff_thresh, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Guidance-mask synthesis of the training loaders on the device (csrc/maskgen.hip; maggie/dataloader/transforms.py:388-565:
+ * GenMaskFromAlpha -> RandomBinarizedMask -> DownUpMask -> CutMask -> MaskDropout). uint8 planes [planes][H][W], H * W < 2^31 (else -2);
+ * every table is DEVICE int32 and is read by the kernel, so a captured launch follows draws written into it between replays. Integer
+ * work: bit-exact, deterministic. No entry synchronises with the host.
+ *   mg_mask_morph : out = 255 * morph(in > thr). params [planes][4] = (thr, k_dilate, k_erode, order): thr = floor of the reference's float
+ *                   threshold (cv2.threshold(THRESH_BINARY) on 8-bit data is v > floor(t)); cv2.dilate / cv2.erode with np.ones((k, k)),
+ *                   anchor a = k / 2: dst[y][x] = max (min) over 0 <= i, j < k of src[y+i-a][x+j-a], pixels outside the image take no part,
+ *                   also between the two passes; 1 <= k <= MG_MASK_MAX_K (the host raises beyond; the kernel clamps); order MG_MASK_*
+ *                   below, MG_MASK_NONE = threshold only (GenMaskFromAlpha is thr = 127 with MG_MASK_NONE). One launch for all planes;
+ *                   threshold and both passes run on a bit-packed tile in LDS.
+ *   mg_mask_downup: where apply[p] != 0: cv2.resize(INTER_LINEAR) to (dh, dw), cv2.resize(INTER_LINEAR) back to (H, W), then 255 * (v > 127);
+ *                   other planes are copied. Any uint8 input. tab = [dw][3] | [dh][3] | [W][3] | [H][3] rows of (offset, c0, c1): the taps
+ *                   `offset` and `offset + 1` (clamped to the last index) and OpenCV's coefficients scaled by 2048, for the columns and rows
+ *                   of the small image and then of the output; horizontal pass row = S0 * c0 + S1 * c1 in int32, vertical pass
+ *                   (((b0 * (R0 >> 4)) >> 16) + ((b1 * (R1 >> 4)) >> 16) + 2) >> 2. The offsets are non-decreasing and a 64-pixel run of the
+ *                   output reads at most MG_MASK_MAX_PATCH of the small image (scale ratio <= 1; the host builds and checks the tables:
+ *                   maggie_amd/utils/maskgen.py resize_tables). The small image stays in LDS. `out` must not alias `in`.
+ *   mg_mask_cut   : out = in with, per plane p, the h x w rectangle at (dst_row, dst_col) replaced by the one at (src_row, src_col) of plane
+ *                   src_plane of `in`. rects [planes][8] = (src_plane, dst_row, dst_col, src_row, src_col, h, w, 0); src_plane < 0 (or a
+ *                   rectangle that leaves the plane) = untouched. CutMask.internal is src_plane = p; .external is two entries naming each
+ *                   other with the same rectangle. Out of place (in == out: -2), so overlapping rectangles read the old values.
+ *   mg_mask_stats : stats [planes][5] = (count, xmin, xmax, ymin, ymax) of the non-zero pixels; an empty plane gives (0, W, -1, H, -1).
+ *   mg_mask_drop  : in place, entry e of sel [n][4] = (plane, idx, ph, pw): (x, y) = the idx-th non-zero pixel of the plane in raster order;
+ *                   x = min(x, xmax - pw), y = min(y, ymax - ph) (not below 0) with this plane's row of `stats`; zero [y, y+ph) x [x, x+pw)
+ *                   (MaskDropout, transforms.py:557-563). plane < 0, idx outside the plane's count, ph <= 0 or pw <= 0 = skipped. The
+ *                   entries name distinct planes.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_MASK_MAX_K 31
+#define MG_MASK_MAX_PATCH 66
+#define MG_MASK_DILATE_ERODE 0
+#define MG_MASK_ERODE_DILATE 1
+#define MG_MASK_DILATE 2
+#define MG_MASK_ERODE 3
+#define MG_MASK_NONE 4
+int mg_mask_morph(const uint8_t* in, uint8_t* out, const int32_t* params, long planes, int H, int W, void* stream);
+int mg_mask_downup(const uint8_t* in, uint8_t* out, const int32_t* apply, const int32_t* tab, int dh, int dw, long planes, int H, int W,
+                   void* stream);
+int mg_mask_cut(const uint8_t* in, uint8_t* out, const int32_t* rects, long planes, int H, int W, void* stream);
+int mg_mask_stats(const uint8_t* in, int32_t* stats, long planes, int H, int W, void* stream);
+int mg_mask_drop(uint8_t* planes_u8, const int32_t* sel, const int32_t* stats, int n, long planes, int H, int W, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

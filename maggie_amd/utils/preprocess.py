@@ -83,10 +83,12 @@ class DevicePreprocessor:
     def __init__(self, max_inst=10, downscale_mask=True, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
         self.max_inst, self.downscale_mask, self.mean, self.std, self.device = max_inst, downscale_mask, mean, std, device
 
-    def __call__(self, frames_u8, alphas_u8=None, masks_u8=None, slot_ids=None, *, transition=None, trimap=False):
+    def __call__(self, frames_u8, alphas_u8=None, masks_u8=None, slot_ids=None, *, transition=None, trimap=False, mask_draws=None):
         """`transition=(k_size, iterations)` adds the training entry 'transition' from the alphas (utils/groundtruth.py): one frame -> the
         per-instance band of him.py:185-189 in the same slots as 'alpha'; a clip (T > 1) -> the frame-difference rule of vim.py:171-183.
-        `trimap=True` adds the evaluation entry 'trimap' (him.py:190-196) from the alphas as given (`ori_alphas`: no `< 5` rule)."""
+        `trimap=True` adds the evaluation entry 'trimap' (him.py:190-196) from the alphas as given (`ori_alphas`: no `< 5` rule).
+        `mask_draws` (a maskgen.MaskDraws for the T * n_i planes, or (MaskDraws, RandomState) when its drop-out is on) sends `masks_u8`
+        through the loaders' mask chain first (utils/maskgen.py `synthesize`); image training passes the alphas as `masks_u8` (him.py:103)."""
         out = {'image': normalize_frames(frames_u8, self.mean, self.std, self.device)}
         T, _, H, W = out['image'].shape
         n_slots = self.max_inst if slot_ids is not None else None
@@ -95,6 +97,10 @@ class DevicePreprocessor:
             out['alpha'] = scale_planes(a, n_slots, slot_ids, None, 5, self.device)                      # transforms.py:744
         if masks_u8 is not None:
             m = masks_u8.reshape(T, -1, H, W)
+            if mask_draws is not None:
+                from . import maskgen
+                draws, dropout_random = mask_draws if isinstance(mask_draws, tuple) else (mask_draws, None)
+                m = maskgen.synthesize(m, draws, dropout_random, device=self.device)
             size = (H // 8, W // 8) if self.downscale_mask else None                                   # him.py:172-173
             out['mask'] = scale_planes(m, n_slots, slot_ids, size, 0, self.device)
         if transition is not None or trimap:

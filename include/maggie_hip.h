@@ -586,6 +586,45 @@ int mg_mask_stats(const uint8_t* in, int32_t* stats, long planes, int H, int W, 
 int mg_mask_drop(uint8_t* planes_u8, const int32_t* sel, const int32_t* stats, int n, long planes, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Input geometry on the device (csrc/geometry.hip; maggie/dataloader/transforms.py:104-166, ResizeShort -> PaddingMultiplyBy): cv2.resize of
+ * uint8 images with the padding and the tensor stage fused into the same launch. Integer work and IEEE divisions: bit-exact.
+ *   mg_resize_u8 : in uint8 [images][H][W][channels] (channels 1 or 3) -> an (Ho, Wo) output per image whose cells (y < dh, x < dw) hold
+ *                  the resized image and whose other cells are the padding: the value a source pixel of 0 would have given.
+ *                  interp MG_RESIZE_LINEAR : xtab [dw][3], ytab [dh][3] DEVICE int32 rows of (offset, c0, c1) as in mg_mask_downup -- taps
+ *                    `offset` and `offset + 1` (clamped to the last index), OpenCV's 11-bit coefficients; the same column table for every
+ *                    channel; row = S0 * c0 + S1 * c1 in int32, then (((b0 * (R0 >> 4)) >> 16) + ((b1 * (R1 >> 4)) >> 16) + 2) >> 2.
+ *                  interp MG_RESIZE_NEAREST: xtab [dw], ytab [dh] DEVICE int32 source indices (cv2.INTER_NEAREST, or any composition of
+ *                    index maps: the mask path folds the resize, the padding and the loaders' nearest 1/8 down-scale into one table).
+ *                  The tables are built on the host (maggie_amd/utils/geometry.py); every index read from them is clamped to the source.
+ *                  epilogue MG_RESIZE_RAW  : out uint8 [images][Ho][Wo][channels].
+ *                           MG_RESIZE_NORM : channels 3; out fp32 [images][3][Ho][Wo] = (v / 255 - mean[c]) / std[c] (the expression of
+ *                                            mg_preprocess_image, shared through csrc/pixel_norm.h); no uint8 intermediate.
+ *                           MG_RESIZE_SLOTS: channels 1; `images` frames of n_in planes -> out fp32 [images][n_slots][Ho][Wo] = v / 255 of
+ *                                            plane src_of_slot[frame * n_slots + slot] (DEVICE int32; < 0 = empty slot -> zeros; NULL =
+ *                                            identity, n_slots == n_in), values below `thresh` -> 0: mg_preprocess_planes' contract.
+ *                  regime (linear only) MG_RESIZE_SHARED_ROWS: the horizontal pass of the source rows of a MG_RESIZE_TILE_ROWS x
+ *                    MG_RESIZE_TILE_COLS output tile runs once into LDS (uint16 per channel and column), the vertical pass reads it; legal
+ *                    when no tile reads more than MG_RESIZE_MAX_ROWS source rows (the host checks its row table; the kernel clamps).
+ *                    MG_RESIZE_DIRECT: four global taps per output pixel, four pixels per lane: any ratio. Both give the same bits.
+ *                  Returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension.
+ *   mg_resize_limits: the tile and LDS row budget of the shared-rows regime, for the host's choice.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_RESIZE_LINEAR 0
+#define MG_RESIZE_NEAREST 1
+#define MG_RESIZE_RAW 0
+#define MG_RESIZE_NORM 1
+#define MG_RESIZE_SLOTS 2
+#define MG_RESIZE_SHARED_ROWS 0
+#define MG_RESIZE_DIRECT 1
+#define MG_RESIZE_TILE_ROWS 32
+#define MG_RESIZE_TILE_COLS 64
+#define MG_RESIZE_MAX_ROWS 68
+int mg_resize_u8(const uint8_t* in, void* out, const int32_t* xtab, const int32_t* ytab, const int32_t* src_of_slot, long images, int n_in,
+                 int n_slots, int channels, int H, int W, int dh, int dw, int Ho, int Wo, int interp, int epilogue, int regime,
+                 const float* mean3, const float* std3, int thresh, void* stream);
+int mg_resize_limits(int* tile_rows, int* tile_cols, int* max_rows);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

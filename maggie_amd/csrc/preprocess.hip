@@ -6,6 +6,7 @@
 // Arithmetic is the reference's, operation for operation (IEEE fp32 divisions, not reciprocal multiplies): bit-exact.
 #include "common.h"
 #include "../../include/maggie_hip.h"
+#include "pixel_norm.h"
 
 namespace {
 
@@ -28,16 +29,16 @@ __global__ __launch_bounds__(256) void preprocess_image_kernel(const uint8_t* __
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float4 v;
-            v.x = __fdiv_rn(__fdiv_rn((float)b[c], 255.0f) - nm.mean[c], nm.std[c]);
-            v.y = __fdiv_rn(__fdiv_rn((float)b[3 + c], 255.0f) - nm.mean[c], nm.std[c]);
-            v.z = __fdiv_rn(__fdiv_rn((float)b[6 + c], 255.0f) - nm.mean[c], nm.std[c]);
-            v.w = __fdiv_rn(__fdiv_rn((float)b[9 + c], 255.0f) - nm.mean[c], nm.std[c]);
+            v.x = mg_norm_u8(b[c], nm.mean[c], nm.std[c]);
+            v.y = mg_norm_u8(b[3 + c], nm.mean[c], nm.std[c]);
+            v.z = mg_norm_u8(b[6 + c], nm.mean[c], nm.std[c]);
+            v.w = mg_norm_u8(b[9 + c], nm.mean[c], nm.std[c]);
             *(float4*)(dst + c * HW) = v;
         }
     } else {
         for (long i = p; i < HW; ++i)
             for (int c = 0; c < 3; ++c)
-                out[f * 3 * HW + c * HW + i] = __fdiv_rn(__fdiv_rn((float)in[(f * HW + i) * 3 + c], 255.0f) - nm.mean[c], nm.std[c]);
+                out[f * 3 * HW + c * HW + i] = mg_norm_u8(in[(f * HW + i) * 3 + c], nm.mean[c], nm.std[c]);
     }
 }
 
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void preprocess_planes_kernel(const uint8_t* _
             const int sy = (Ho == H) ? y : min((int)floorf(y * sh), H - 1);
             const int sx = (Wo == W) ? x : min((int)floorf(x * sw), W - 1);
             const int u = plane[(long)sy * W + sx];
-            v = u < thresh ? 0.f : __fdiv_rn((float)u, 255.0f);
+            v = mg_scale_u8(u, thresh);
         }
         o[i] = v;
     }

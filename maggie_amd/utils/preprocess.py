@@ -117,3 +117,65 @@ class DevicePreprocessor:
             if trimap:
                 out['trimap'] = groundtruth.trimap(a, self.device)
         return out
+
+    def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):
+        """The evaluation item of him.py:151-202 / vim.py:150-209 from decoded files: (T, h, w, 3) uint8 frames (a clip of T equal-sized
+        frames in one call; (h, w, 3) is T = 1), (T, n_i, h, w) `ori_alphas`, optionally (T, n_i, h, w) guidance masks of a mask directory.
+          'image'  (T, 3, Hp, Wp): ResizeShort + PaddingMultiplyBy + Normalize in one launch (utils/geometry.py), no uint8 intermediate;
+          'mask'   from `masks_u8` by nearest resize, padding, the nearest 1/8 of him.py:175-176 when `downscale_mask` is set, `/ 255`, as one
+                   index map; without `masks_u8`, from the resized and padded alphas through `maskgen.from_alpha` (him.py:58-59);
+          'alpha'  `ori_alphas / 255` at the original size, no `< 5` rule (him.py:152);
+          'trimap' from the original alphas (utils/groundtruth.py);
+          'transform_info' the list `postprocessing.reverse_transform_tensor` reads."""
+        from . import geometry, groundtruth
+        frames = groundtruth._check_u8(frames_u8)
+        if frames.dim() == 3:
+            frames = frames[None]
+        if frames.dim() != 4 or frames.shape[-1] != 3:
+            raise ValueError('frames must be (T, h, w, 3) or (h, w, 3) (got shape %s)' % (tuple(frames.shape),))
+        T, h, w = (int(v) for v in frames.shape[:3])
+        p = geometry.plan(h, w, short_size, divisor)
+        a = self._item_planes(ori_alphas_u8, T, h, w, 'ori_alphas')
+        m = None if masks_u8 is None else self._item_planes(masks_u8, T, h, w, 'masks')
+        if m is not None and m.shape[1] != a.shape[1]:
+            raise ValueError('masks: expected %d planes per frame like the alphas (got %d)' % (a.shape[1], m.shape[1]))
+        image, _ = geometry.resize_pad_normalize(frames, p, mean=self.mean, std=self.std, device=self.device)
+        out = {'image': image}
+        if m is not None:
+            out['mask'] = geometry.resize_pad_planes(m, p, interpolation='nearest', down8=self.downscale_mask, device=self.device)
+        else:
+            from . import maskgen
+            g = maskgen.from_alpha(geometry.resize_pad_planes_u8(a, p, device=self.device), device=self.device)
+            size = (p.out_h // 8, p.out_w // 8) if self.downscale_mask else None
+            out['mask'] = scale_planes(g, None, None, size, 0, self.device)
+        out['alpha'] = scale_planes(a, None, None, None, 0, self.device)
+        if trimap:
+            out['trimap'] = groundtruth.trimap(a, self.device)
+        out['transform_info'] = p.transform_info
+        return out
+
+    def predict_item(self, frame_u8, instance_masks_u8, *, short_size=576, divisor=64):
+        """demo/maggie_predictor.py:34-50: one (h, w, 3) uint8 frame and its (n, h, w) uint8 instance masks (0 / 255) ->
+        ({'image': (1, 1, 3, Hp, Wp), 'mask': (1, 1, n, Hp, Wp)}, transform_info); the masks keep the network's full size there."""
+        from . import geometry, groundtruth
+        frame = groundtruth._check_u8(frame_u8)
+        if frame.dim() != 3 or frame.shape[-1] != 3:
+            raise ValueError('frame must be (h, w, 3) (got shape %s)' % (tuple(frame.shape),))
+        h, w = (int(v) for v in frame.shape[:2])
+        p = geometry.plan(h, w, short_size, divisor)
+        m = self._item_planes(instance_masks_u8, 1, h, w, 'instance_masks')
+        image, _ = geometry.resize_pad_normalize(frame[None], p, mean=self.mean, std=self.std, device=self.device)
+        mask = geometry.resize_pad_planes(m, p, interpolation='nearest', device=self.device)
+        return {'image': image[None], 'mask': mask[None]}, p.transform_info
+
+    @staticmethod
+    def _item_planes(x_u8, T, h, w, what):
+        """uint8 (T, n, h, w) or (T * n, h, w) planes of an item, n >= 1 -> (T, n, h, w)."""
+        from . import groundtruth
+        x = groundtruth._check_u8(x_u8)
+        if x.dim() not in (3, 4) or tuple(x.shape[-2:]) != (h, w):
+            raise ValueError('%s: expected (T, n, %d, %d) or (T * n, %d, %d) planes like the frames (got shape %s)' % (what, h, w, h, w, tuple(x.shape)))
+        count = int(np.prod(x.shape[:-2]))
+        if count < 1 or count % T or (x.dim() == 4 and x.shape[0] != T):
+            raise ValueError('%s: %d planes do not make %d frames of at least one instance' % (what, count, T))
+        return x.reshape(T, count // T, h, w)

@@ -182,6 +182,17 @@ typedef struct mg_wgrad_parked {
 int mg_conv_wgrad_park(const mg_conv_params* p, float* workspace, long workspace_floats, mg_wgrad_parked* out, void* stream);
 int mg_wgrad_reduce_batched(const mg_wgrad_parked* items, int count, void* stream);
 
+/* Which kernel forms ran (host-side bookkeeping for tests and tools; needs no GPU). Every kernel form the convolution family compiles has an id in
+ * [0, mg_conv_form_count()) and a stable name: the launcher, its integer template arguments, then the mode where the kernel is templated on it and
+ * the variants it was instantiated with -- "h3<8,64,3>/CONV/res/xf", "fprop<128,64,2>/TCONV/phased", "split<128>/CONV", "split_finish",
+ * "wgrad<32,64>/GATHER", "reduce_tile". The storage type is not part of the name. mg_conv_form_name writes the name (NUL-terminated, truncated to
+ * `cap`) and returns its length, -1 for an unknown id. mg_conv_last_forms writes the ids, in launch order, of the kernels the calling thread's most
+ * recent mg_conv_fprop[_ws], mg_conv_wgrad[_ws | _park] or mg_wgrad_reduce_batched call launched (at most `cap` of them; -1 = a form missing from the
+ * list) and returns how many there were; each of those calls clears the record on entry. */
+int mg_conv_form_count(void);
+int mg_conv_form_name(int id, char* buf, int cap);
+int mg_conv_last_forms(int* ids, int cap);
+
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Row x channel normalisation / activation kernels (HBM-bound, 16-byte vector accesses).

@@ -20,6 +20,7 @@
 // (slot = chunk ^ 3 * ((row >> 3) & 1)), both conflict-free for ds_read_b128 (as in conv_igemm.hip).
 #include "common.h"
 #include "conv_xcd.h"
+#include "conv_forms.h"
 #include "../../include/maggie_hip.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -1089,7 +1090,8 @@ int launch_h3_slab(const mg_conv_params& p, hipStream_t st) {
     if (mg_det_on && p.stats && p.stat_mode == 0 && (long)(p.stat_rep > 0 ? p.stat_rep : MG_STAT_REPLICAS) < tiles) return -8;
     const long maxwg = 3l * ncu, per = (tiles + maxwg - 1) / maxwg;
     dim3 grid(xcd_grid((tiles + per - 1) / per));
-#define H3_SLAB(MODE_, RES_, XF_) hipLaunchKernelGGL((conv_halo3_slab_kernel<T, MODE_, RES_, XF_>), grid, dim3(256), lds, st, p)
+#define H3_SLAB(MODE_, RES_, XF_) do { MG_FORM(MG_FF_H3_SLAB, 0, 0, 0, 0, MODE_, (RES_ ? MG_FORM_RES : 0) | (XF_ ? MG_FORM_XF : 0)); \
+        hipLaunchKernelGGL((conv_halo3_slab_kernel<T, MODE_, RES_, XF_>), grid, dim3(256), lds, st, p); } while (0)
     if (p.xf_scale) {
         if (p.mode != MG_MODE_CONV) return MG_XF_UNSUPPORTED;
         if (res) H3_SLAB(MG_MODE_CONV, true, true); else H3_SLAB(MG_MODE_CONV, false, true);
@@ -1132,6 +1134,7 @@ int launch_h3(const mg_conv_params& p, hipStream_t st) {
             (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xf);
             xf_attr = true;
         }
+        MG_FORM(MG_FF_H3, TH, BN, NS, 0, MG_MODE_CONV, MG_FORM_XF | (res ? MG_FORM_RES : 0));
         if (res) hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true, true>), grid, dim3(NS > 1 ? 512 : 256), lds_xf, st, p);
         else hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false, true>), grid, dim3(NS > 1 ? 512 : 256), lds_xf, st, p);
         MG_CHECK_LAUNCH();
@@ -1144,10 +1147,12 @@ int launch_h3(const mg_conv_params& p, hipStream_t st) {
             (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             bnb_attr = true;
         }
+        MG_FORM(MG_FF_H3, TH, BN, NS, 0, MG_MODE_TCONV, MG_FORM_RES | MG_FORM_BNB);
         hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true, false, true>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
         MG_CHECK_LAUNCH();
         return 0;
     }
+    MG_FORM(MG_FF_H3, TH, BN, NS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, res ? MG_FORM_RES : 0);
     if (p.mode == MG_MODE_CONV) {
         if (res) hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
         else hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
@@ -1182,6 +1187,7 @@ int launch_h3_persist(const mg_conv_params& p, hipStream_t st) {
     if (mg_det_on && p.stats && p.stat_mode == 0 && (long)(p.stat_rep > 0 ? p.stat_rep : MG_STAT_REPLICAS) < mtiles) return -8;
     long g = tiles < ncu ? tiles : ncu;
     dim3 grid(xcd_grid(g));
+    MG_FORM(MG_FF_H3_PERSIST, TH, BN, NS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, res ? MG_FORM_RES : 0);
     if (p.mode == MG_MODE_CONV) {
         if (res) hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, true>), grid, dim3(512), lds, st, p);
         else hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, false>), grid, dim3(512), lds, st, p);
@@ -1226,15 +1232,13 @@ int dispatch_h3(const mg_conv_params& p, hipStream_t st) {
     if (ns >= 200 || p.Cout < 16) return 1;
     if (ns >= 100) {                                         // persistent ring forms (forced: mg_set_halo3_cfg(TH, BN, 100 + NS); chosen: see above)
         if (p.xf_scale || p.bnb_x || (nstage & 1)) return 1;
-        if (th == 8 && bn == 64 && ns == 103) return launch_h3_persist<T, 8, 64, 3>(p, st);
-        if (th == 8 && bn == 32 && ns == 104) return launch_h3_persist<T, 8, 32, 4>(p, st);
+#define H3_PCASE(TH_, BN_, NS_) if (th == TH_ && bn == BN_ && ns == 100 + NS_) return launch_h3_persist<T, TH_, BN_, NS_>(p, st);
+        MG_H3_PERSIST_FORMS(H3_PCASE)
+#undef H3_PCASE
         return 1;
     }
 #define H3_CASE(TH_, BN_, NS_) if (th == TH_ && bn == BN_ && ns == NS_) return launch_h3<T, TH_, BN_, NS_>(p, st);
-    H3_CASE(8, 64, 3) H3_CASE(8, 64, 1) H3_CASE(8, 32, 4) H3_CASE(8, 32, 1) H3_CASE(4, 32, 4)
-#ifdef MG_H3_EXTRA_FORMS
-    H3_CASE(8, 64, 2) H3_CASE(8, 32, 2) H3_CASE(4, 64, 3)
-#endif
+    MG_H3_TILE_FORMS(H3_CASE)
 #undef H3_CASE
     return 1;
 }

@@ -17,6 +17,7 @@
 // BatchNorm statistics (sum, sum of squares) are reduced per block before one atomicAdd per channel.
 #include "common.h"
 #include "conv_xcd.h"
+#include "conv_forms.h"
 #include "../../include/maggie_hip.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -1220,6 +1221,7 @@ static int launch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
                 hipFuncSetAttribute((const void*)igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xf);
                 xf_attr = true;
             }
+            MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, MG_FORM_XF);
             hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T, true>), grid, dim3(256), lds_xf, st, p);
             MG_CHECK_LAUNCH();
             return 0;
@@ -1227,9 +1229,15 @@ static int launch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
     }
     if (p.bnb_x) {                                           // the data gradient of a 3x3 / stride 1 conv behind a BatchNorm layer
         if (p.mode != MG_MODE_TCONV) return -2;
+        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, MG_FORM_BNB);
         hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, true, T>), grid, dim3(256), lds, st, p);
-    } else if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p);
-    else hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p);
+    } else if (p.mode == MG_MODE_CONV) {
+        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, 0);
+        hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p);
+    } else {
+        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, 0);
+        hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p);
+    }
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -1282,6 +1290,7 @@ int launch_fprop_async(const mg_conv_params& p, hipStream_t st) {
     if (int rcs = stat_rows_check(p, (p.M + BM - 1) / BM)) return rcs;
     if (p.bnb_x) {                                           // data gradient of a 1x1 conv behind a BatchNorm layer
         if (p.m_dev || p.mode != MG_MODE_TCONV) return -2;
+        MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, MG_MODE_TCONV, MG_FORM_BNB);
         hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, true, T>), dim3(xcd_grid(tiles)), dim3(256), lds, st, p);
         MG_CHECK_LAUNCH();
         return 0;
@@ -1289,6 +1298,7 @@ int launch_fprop_async(const mg_conv_params& p, hipStream_t st) {
     if (p.m_dev) {
         const long g = tiles < 2048 ? tiles : 2048;
         dim3 pg(xcd_grid(g < 1 ? 1 : g));
+        if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_GATHER) MG_FORM(MG_FF_ASYNC_MDEV, BM, BN, KS, NS, p.mode, 0);
         if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_CONV, T>), pg, dim3(256), lds, st, p);
         else if (p.mode == MG_MODE_GATHER) hipLaunchKernelGGL((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_GATHER, T>), pg, dim3(256), lds, st, p);
         else return -2;
@@ -1296,6 +1306,7 @@ int launch_fprop_async(const mg_conv_params& p, hipStream_t st) {
         return 0;
     }
     dim3 grid(xcd_grid(tiles));
+    if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, p.mode, 0);
     switch (p.mode) {
         case MG_MODE_CONV: hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p); break;
         case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p); break;
@@ -1344,6 +1355,7 @@ int launch_fprop(const mg_conv_params& p, hipStream_t st) {
     }
     if (p.bnb_x) {                                           // a data-gradient launch that also accumulates a BatchNorm layer's backward sums
         if (p.m_dev) return -2;
+        if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_TCONV) MG_FORM(MG_FF_FPROP, BM, BN, KS, 0, p.mode, MG_FORM_BNB | (tconv_phased(p) ? MG_FORM_PHASED : 0));
         if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
         else if (p.mode == MG_MODE_TCONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
         else return -2;
@@ -1364,12 +1376,14 @@ int launch_fprop(const mg_conv_params& p, hipStream_t st) {
         if (p.xf_scale) {                                    // sparse head: BatchNorm1d + activation of the producing layer applied on the operand's way into LDS
             if constexpr (sizeof(T) == 2 && BM == 128 && BN <= 32 && KS <= 2) {
                 if (!fprop_xf_rows_ok(p)) return MG_XF_UNSUPPORTED;
+                MG_FORM(MG_FF_FPROP_MDEV, BM, BN, KS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_GATHER, MG_FORM_XF);
                 if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), pg, dim3(256), lds, st, p);
                 else hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER, true>), pg, dim3(256), lds, st, p);
                 MG_CHECK_LAUNCH();
                 return 0;
             } else return MG_XF_UNSUPPORTED;
         }
+        if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_GATHER) MG_FORM(MG_FF_FPROP_MDEV, BM, BN, KS, 0, p.mode, 0);
         if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV>), pg, dim3(256), lds, st, p);
         else if (p.mode == MG_MODE_GATHER) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER>), pg, dim3(256), lds, st, p);
         else return -2;
@@ -1377,6 +1391,7 @@ int launch_fprop(const mg_conv_params& p, hipStream_t st) {
         return 0;
     }
     if (p.xf_scale) return MG_XF_UNSUPPORTED;
+    if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_FPROP, BM, BN, KS, 0, p.mode, tconv_phased(p) ? MG_FORM_PHASED : 0);
     switch (p.mode) {
         case MG_MODE_CONV: hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
         case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
@@ -1577,6 +1592,7 @@ static int launch_fprop_split(const mg_conv_params& p, float* ws, int splits, hi
         hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
+    MG_FORM(MG_FF_SPLIT, BN, 0, 0, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, 0);
     if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), grid, dim3(256), lds, st, p, ws, splits);
     else hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, true>), grid, dim3(256), lds, st, p, ws, splits);
     MG_CHECK_LAUNCH();
@@ -1588,6 +1604,7 @@ static int launch_fprop_split(const mg_conv_params& p, float* ws, int splits, hi
     if (rb > 512) rb = 512;
     const int rpb = (p.M + rb - 1) / rb;
     if (int rcs = stat_rows_check(p, (p.M + rpb - 1) / rpb)) return rcs;
+    MG_FORM(MG_FF_SPLIT_FINISH, 0, 0, 0, 0, MG_FORM_NOMODE, 0);
     hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3((p.M + rpb - 1) / rpb, groups), dim3(256), 0, st, p, (const float*)ws, splits, rpb);
     MG_CHECK_LAUNCH();
     return 0;
@@ -1675,10 +1692,12 @@ static int launch_fprop_c8(const mg_conv_params& p, hipStream_t st) {
     if (th == 16) {
         const long tiles = (long)p.N * ((p.Hout + 15) / 16) * ((p.Wout + 15) / 16);
         const size_t lds = (size_t)ctile_bytes<256, 32>() + (18 * 18 + 1) * 16;
+        MG_FORM(MG_FF_C8, 16, 0, 0, 0, MG_FORM_NOMODE, 0);
         hipLaunchKernelGGL((igemm_fprop_c8_kernel<16, T>), dim3(xcd_grid(tiles)), dim3(256), lds, st, p);
     } else {
         const long tiles = (long)p.N * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16);
         const size_t lds = (size_t)ctile_bytes<128, 32>() + (10 * 18 + 1) * 16;
+        MG_FORM(MG_FF_C8, 8, 0, 0, 0, MG_FORM_NOMODE, 0);
         hipLaunchKernelGGL((igemm_fprop_c8_kernel<8, T>), dim3(xcd_grid(tiles)), dim3(256), lds, st, p);
     }
     MG_CHECK_LAUNCH();
@@ -1807,6 +1826,7 @@ extern "C" int mg_conv_halo3(const mg_conv_params* pp, void* stream);        // 
 
 extern "C" int mg_conv_fprop_ws(const mg_conv_params* pp, float* workspace, long workspace_floats, void* stream) {
     if (!pp) return -1;
+    mg_conv_forms_clear();
     const mg_conv_params& p = *pp;
     if (p.M <= 0) return 0;
     // the 3x3 / stride-1 layers of the 16 x 16 and 32 x 32 maps: the round-6 halo form (4 x 16 pixel tiles, four-slab ring) beats split-K + finish
@@ -1824,6 +1844,7 @@ extern "C" int mg_conv_fprop_ws(const mg_conv_params* pp, float* workspace, long
 
 extern "C" int mg_conv_fprop(const mg_conv_params* pp, void* stream) {
     if (!pp) return -1;
+    mg_conv_forms_clear();
     const mg_conv_params& p = *pp;
     if (p.M <= 0) return 0;
     { int rc = conv_fprop_check(p); if (rc) return rc; }

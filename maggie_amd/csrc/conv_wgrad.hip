@@ -2,6 +2,7 @@
 // conv_igemm.hip and these compile in parallel). Entry points: mg_conv_wgrad_workspace, mg_conv_wgrad_ws, mg_conv_wgrad.
 #include "common.h"
 #include "conv_xcd.h"
+#include "conv_forms.h"
 #include "../../include/maggie_hip.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -336,9 +337,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const RedTabl
 #define MG_REDUCE_LAUNCH(KERN, B, WS, SPLITS)                                                                                                          \
     do {                                                                                                                                               \
         if (g_park.on) { g_park.ws = (WS); g_park.n = n; g_park.splits = (int)(SPLITS); g_park.form = RED_FORM_##KERN; g_park.blocks = (long)(B); }    \
-        else if (p.dw_dtype == MG_BF16) hipLaunchKernelGGL(KERN<bf16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (bf16raw*)p.stats);  \
-        else if (p.dw_dtype == MG_F16) hipLaunchKernelGGL(KERN<f16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (f16raw*)p.stats); \
-        else hipLaunchKernelGGL(KERN<float>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, p.stats);                                    \
+        else {                                                                                                                                         \
+            MG_FORM(RED_FORM_##KERN == 0 ? MG_FF_REDUCE : RED_FORM_##KERN == 1 ? MG_FF_REDUCE_WAVE : MG_FF_REDUCE_TILE, 0, 0, 0, 0, MG_FORM_NOMODE, 0); \
+            if (p.dw_dtype == MG_BF16) hipLaunchKernelGGL(KERN<bf16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (bf16raw*)p.stats); \
+            else if (p.dw_dtype == MG_F16) hipLaunchKernelGGL(KERN<f16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (f16raw*)p.stats); \
+            else hipLaunchKernelGGL(KERN<float>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, p.stats);                                \
+        }                                                                                                                                              \
     } while (0)
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -676,6 +680,7 @@ static int launch_wgrad_gather9(const mg_conv_params& p, float* ws, long ws_floa
     }
     if (p.xf_scale) {                                        // x = a raw conv output, BatchNorm1d + activation applied on the way into LDS
         if (tco != 32) return MG_XF_UNSUPPORTED;
+        MG_FORM(MG_FF_WGRAD_GATHER9, 1, 0, 0, 0, MG_FORM_NOMODE, MG_FORM_XF);
         static bool xattr = false;
         if (!xattr) {
             (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<1, bf16raw, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
@@ -684,11 +689,14 @@ static int launch_wgrad_gather9(const mg_conv_params& p, float* ws, long ws_floa
         }
         if (p.dtype == MG_F16) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, f16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
         else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, bf16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
-    } else if (p.dtype == MG_F16) {
-        if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
-        else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
-    } else if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2>), grid, dim3(256), lds, st, p, (int)splits, ws);
-    else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1>), grid, dim3(256), lds, st, p, (int)splits, ws);
+    } else {
+        MG_FORM(MG_FF_WGRAD_GATHER9, tco / 32, 0, 0, 0, MG_FORM_NOMODE, 0);
+        if (p.dtype == MG_F16) {
+            if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
+            else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        } else if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1>), grid, dim3(256), lds, st, p, (int)splits, ws);
+    }
     if (splits >= 8) {
         const long b = (n + 31) / 32;
         MG_REDUCE_LAUNCH(wgrad_reduce_tile_kernel, b, ws, splits);
@@ -822,6 +830,7 @@ static int launch_wgrad_c8(const mg_conv_params& p, float* ws, long ws_floats, h
     if (!ws || ws_floats < splits * n) return -4;
     dim3 grid(xcd_grid(splits * (p.Cout / 32)));
     const size_t lds = (size_t)(8 * 16 * (32 + 16) + (10 * 18 + 4) * 8) * sizeof(bf16raw);
+    MG_FORM(MG_FF_WGRAD_C8, 0, 0, 0, 0, MG_FORM_NOMODE, 0);
     if (p.dtype == MG_F16) hipLaunchKernelGGL(igemm_wgrad_c8_kernel<f16raw>, grid, dim3(256), lds, st, p, tpb, ws);
     else hipLaunchKernelGGL(igemm_wgrad_c8_kernel<bf16raw>, grid, dim3(256), lds, st, p, tpb, ws);
     const long b = (n + 31) / 32;
@@ -868,6 +877,7 @@ static int launch_wgrad_halo(const mg_conv_params& p, float* ws, long ws_floats,
     const long cc = (long)(p.Cin / 32) * (p.Cout / 32);
     dim3 grid(xcd_grid(pl.splits * cc));
     const size_t lds = (size_t)(8 * 16 * (32 + 16) + 10 * 18 * (32 + 16)) * sizeof(bf16raw);
+    MG_FORM(MG_FF_WGRAD_HALO, 0, 0, 0, 0, MG_FORM_NOMODE, p.xf_scale ? MG_FORM_XF : 0);
     if (p.xf_scale) {
         if (p.dtype == MG_F16) hipLaunchKernelGGL((igemm_wgrad_halo_kernel<1, 1, f16raw, true>), grid, dim3(256), lds, st, p, pl.tpb, use_ws);
         else hipLaunchKernelGGL((igemm_wgrad_halo_kernel<1, 1, bf16raw, true>), grid, dim3(256), lds, st, p, pl.tpb, use_ws);
@@ -944,16 +954,19 @@ int launch_wgrad(const mg_conv_params& p, float* ws, long ws_floats, hipStream_t
     size_t lds = stage > red ? stage : red;
     if (p.xf_scale) {
         if constexpr (BF && TCO == 32 && TCI == 32) {
+            if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_GATHER) MG_FORM(MG_FF_WGRAD, TCO, TCI, 0, 0, p.mode, MG_FORM_XF);
             if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_CONV, true>), grid, dim3(256), lds, st, q, pl.rpb, use_ws);
             else if (p.mode == MG_MODE_GATHER) hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_GATHER, true>), grid, dim3(256), lds, st, q, pl.rpb, use_ws);
             else return MG_XF_UNSUPPORTED;
         } else return MG_XF_UNSUPPORTED;
-    } else
-    switch (p.mode) {
-        case MG_MODE_CONV: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_CONV>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
-        case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_TCONV>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
-        case MG_MODE_GATHER: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_GATHER>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
-        default: return -2;
+    } else {
+        if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_WGRAD, TCO, TCI, 0, 0, p.mode, 0);
+        switch (p.mode) {
+            case MG_MODE_CONV: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_CONV>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
+            case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_TCONV>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
+            case MG_MODE_GATHER: hipLaunchKernelGGL((igemm_wgrad_kernel<T, TCO, TCI, MG_MODE_GATHER>), grid, dim3(256), lds, st, q, pl.rpb, use_ws); break;
+            default: return -2;
+        }
     }
     if (use_ws && (pl.splits > 1 || out_bf16)) {
         if (pl.splits > 32 && n <= (1l << 16)) {
@@ -1040,6 +1053,7 @@ extern "C" long mg_conv_wgrad_workspace(const mg_conv_params* pp) {
 // dW (fp32, p->stats) is fully OVERWRITTEN when a sufficient workspace is given (two-stage reduction over row splits);
 // without workspace it is accumulated with atomics and must be pre-zeroed.
 extern "C" int mg_conv_wgrad_ws(const mg_conv_params* pp, float* workspace, long workspace_floats, void* stream) {
+    mg_conv_forms_clear();
     int rc = wgrad_check(pp);
     if (rc) return rc;
     if (!pp->stats) return -4;
@@ -1072,6 +1086,7 @@ extern "C" int mg_conv_wgrad_park(const mg_conv_params* pp, float* workspace, lo
 }
 
 extern "C" int mg_wgrad_reduce_batched(const mg_wgrad_parked* items, int count, void* stream) {
+    mg_conv_forms_clear();
     if (count <= 0) return 0;
     if (!items) return -1;
     hipStream_t st = (hipStream_t)stream;
@@ -1081,6 +1096,7 @@ extern "C" int mg_wgrad_reduce_batched(const mg_wgrad_parked* items, int count, 
     auto flush = [&]() -> int {
         if (k == 0) return 0;
         tb.count = k;
+        MG_FORM(MG_FF_REDUCE_BATCHED, 0, 0, 0, 0, MG_FORM_NOMODE, 0);
         hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(blocks), dim3(256), 0, st, tb);
         k = 0; blocks = 0;
         hipError_t e = hipGetLastError();

@@ -274,6 +274,36 @@ def wgrad_reduce_batched(park):
     del park[:]
 
 
+_FORM_NAMES = []
+
+
+def conv_form_names():
+    """Names of every kernel form the convolution family compiles, indexed by form id (mg_conv_form_count / mg_conv_form_name). Needs no GPU."""
+    if not _FORM_NAMES:
+        lib = hip.lib()
+        lib.mg_conv_form_count.restype = ctypes.c_int
+        lib.mg_conv_form_name.restype = ctypes.c_int
+        buf = ctypes.create_string_buffer(128)
+        for i in range(lib.mg_conv_form_count()):
+            n = lib.mg_conv_form_name(c_int(i), buf, c_int(len(buf)))
+            assert 0 < n < len(buf), (i, n)
+            _FORM_NAMES.append(buf.value.decode())
+    return list(_FORM_NAMES)
+
+
+def conv_last_forms():
+    """Names of the kernel forms the calling thread's most recent conv_fprop / conv_wgrad / wgrad_reduce_batched call launched, in launch order
+    (mg_conv_last_forms). Host-side bookkeeping: no synchronisation."""
+    names = conv_form_names()
+    lib = hip.lib()
+    lib.mg_conv_last_forms.restype = ctypes.c_int
+    ids = (ctypes.c_int * 32)()
+    n = lib.mg_conv_last_forms(ids, c_int(32))
+    if n > 32:
+        raise hip.MaggieHipError('mg_conv_last_forms: %d launches, more than the record holds' % n)
+    return [names[ids[i]] if 0 <= ids[i] < len(names) else '?' for i in range(n)]
+
+
 _WS = {}
 
 

@@ -636,6 +636,43 @@ int mg_resize_u8(const uint8_t* in, void* out, const int32_t* xtab, const int32_
 int mg_resize_limits(int* tile_rows, int* tile_cols, int* max_rows);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Training crop on the device (csrc/crop.hip; maggie/dataloader/transforms.py:191-305, RandomCropByAlpha -> RandomHorizontalFlip, between
+ * PaddingMultiplyBy and the mask chain). uint8 in; integer work and the IEEE divisions of csrc/pixel_norm.h: bit-exact. The draws stay on the
+ * host (maggie_amd/utils/crop.py); the kernels read them from DEVICE int32 tables, so a captured launch follows draws written between replays.
+ *   mg_crop_bbox     : alphas uint8 [planes][H][W] -> box [5] = (count, xmin, xmax, ymin, ymax) of the pixels whose sum over all planes exceeds
+ *                      127 * planes (`alphas.mean(0) > 127` as an integer test); no such pixel gives (0, W, -1, H, -1). Rows are split over
+ *                      many workgroups: per-workgroup extremes in LDS, then integer atomics on the five words (which the entry initialises
+ *                      on the stream first). planes <= MG_CROP_MAX_PLANES.
+ *   mg_crop_hits     : hits [n] = 1 where any plane holds a value > 127 inside window k = [y0, y0 + ch) x [x0, x0 + cw), windows [n][2] =
+ *                      (x0, y0), n <= MG_CROP_MAX_WINDOWS; otherwise 0. Reads the windows only.
+ *   mg_crop_gather   : out pixel (y, x) of image i = in pixel (y0 + y, x0 + x), or (y0 + y, x0 + cw - 1 - x) when flip != 0; window [3] =
+ *                      (x0, y0, flip), one for all images, clamped to the source. in uint8 [images][H][W][channels] (channels 1 or 3).
+ *                      lut (channels 3 only, or NULL): DEVICE uint8 [3][256], v = lut[c][v] after the gather and before the epilogue.
+ *                      epilogue MG_CROP_RAW : out uint8 [images][ch][cw][channels];
+ *                               MG_CROP_NORM: channels 3; out fp32 [images][3][ch][cw] = (v / 255 - mean[c]) / std[c], the bits of
+ *                                             mg_preprocess_image on the uint8 crop.
+ *                      A lane owns MG_CROP_CHUNK pixels of one output row: 16-byte stores when cw is a multiple of it, per element otherwise.
+ *   mg_crop_padresize: the padding branch: cv2.resize of the image padded with zeros by (pad_h, pad_w) on both sides to (dh, dw). The tables
+ *                      are those of mg_resize_u8 (linear xtab [dw][3], ytab [dh][3]; nearest xtab [dw], ytab [dh]) in PADDED coordinates;
+ *                      the kernel subtracts the pads and reads 0 outside the source. A flip is a reversed column table. Epilogues and lut as
+ *                      in mg_crop_gather with (ch, cw) = (dh, dw).
+ * Each returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_CROP_RAW 0
+#define MG_CROP_NORM 1
+#define MG_CROP_MAX_WINDOWS 3
+#define MG_CROP_MAX_PLANES (1 << 22)
+#define MG_CROP_CHUNK 16
+int mg_crop_bbox(const uint8_t* alphas, int32_t* box, long planes, int H, int W, void* stream);
+int mg_crop_hits(const uint8_t* alphas, const int32_t* windows, int32_t* hits, int n, long planes, int H, int W, int ch, int cw, void* stream);
+int mg_crop_gather(const uint8_t* in, void* out, const int32_t* window, const uint8_t* lut, long images, int channels, int H, int W, int ch,
+                   int cw, int epilogue, const float* mean3, const float* std3, void* stream);
+int mg_crop_padresize(const uint8_t* in, void* out, const int32_t* xtab, const int32_t* ytab, const uint8_t* lut, long images, int channels,
+                      int H, int W, int pad_h, int pad_w, int dh, int dw, int interp, int epilogue, const float* mean3, const float* std3,
+                      void* stream);
+int mg_crop_limits(int* max_windows, int* max_planes, int* chunk);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

@@ -89,7 +89,12 @@ class DevicePreprocessor:
         `trimap=True` adds the evaluation entry 'trimap' (him.py:190-196) from the alphas as given (`ori_alphas`: no `< 5` rule).
         `mask_draws` (a maskgen.MaskDraws for the T * n_i planes, or (MaskDraws, RandomState) when its drop-out is on) sends `masks_u8`
         through the loaders' mask chain first (utils/maskgen.py `synthesize`); image training passes the alphas as `masks_u8` (him.py:103)."""
-        out = {'image': normalize_frames(frames_u8, self.mean, self.std, self.device)}
+        return self._assemble(normalize_frames(frames_u8, self.mean, self.std, self.device), alphas_u8, masks_u8, slot_ids, transition, trimap,
+                              mask_draws)
+
+    def _assemble(self, image, alphas_u8, masks_u8, slot_ids, transition, trimap, mask_draws):
+        """The entries of `__call__` around an `image` that is already the normalised (T, 3, H, W) tensor."""
+        out = {'image': image}
         T, _, H, W = out['image'].shape
         n_slots = self.max_inst if slot_ids is not None else None
         if alphas_u8 is not None:
@@ -117,6 +122,21 @@ class DevicePreprocessor:
             if trimap:
                 out['trimap'] = groundtruth.trimap(a, self.device)
         return out
+
+    def train_item(self, frames_u8, alphas_u8, masks_u8, crop_draws, slot_ids=None, *, transition=None, mask_draws=None, lut=None):
+        """The training item of him.py:36-65 / vim.py:43-74 from the stacked uint8 arrays after PaddingMultiplyBy (`geometry.resize_short_pad`):
+        RandomCropByAlpha + RandomHorizontalFlip from `crop_draws` (a crop.CropDraws: `crop.draw_on_device`), then what `__call__` does on the
+        crops -- the mask chain of `mask_draws` (made for the cropped size), `/ 255` into the slots, `transition`. 'image' comes from the crop's
+        own Normalize epilogue: the uint8 crop of the frames is never stored. `lut`: a (3, 256) uint8 tone curve for the frames (utils/crop.py).
+        Image training passes the alphas as `masks_u8` too (him.py:103); the same object is cropped once."""
+        from . import crop
+        if len(frames_u8.shape) != 4:
+            raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
+        image, a, m = crop.apply(frames_u8, alphas_u8, None if masks_u8 is alphas_u8 else masks_u8, crop_draws, normalize=True, lut=lut,
+                                 mean=self.mean, std=self.std, device=self.device)
+        if masks_u8 is alphas_u8:
+            m = a
+        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
 
     def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):
         """The evaluation item of him.py:151-202 / vim.py:150-209 from decoded files: (T, h, w, 3) uint8 frames (a clip of T equal-sized

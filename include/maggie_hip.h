@@ -673,6 +673,44 @@ int mg_crop_padresize(const uint8_t* in, void* out, const int32_t* xtab, const i
 int mg_crop_limits(int* max_windows, int* max_planes, int* chunk);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * RandomAffine on the device (csrc/affine.hip; maggie/dataloader/transforms.py:926-963 with dataloader/utils.py:61-221: cv2.warpAffine of
+ * every frame and alpha plane of an item, then the float64 channel shift of the frames). uint8 in; the warp is integer work only, the shift is
+ * the reference's float64 add and clamp followed by the IEEE divisions of csrc/pixel_norm.h: bit-exact. The draws, the matrix, its inversion
+ * and the tables stay on the host (maggie_amd/utils/affine.py); the kernels read DEVICE buffers, so a captured launch follows draws written
+ * between replays.
+ *   tab              : DEVICE int32 [adelta W | bdelta W | X0 H | Y0 H], OpenCV's AB_BITS = 10 tables of the INVERSE map for an (H, W)
+ *                      destination of the source's size: adelta[x] = cvRound(M0 * x * 1024), bdelta[x] = cvRound(M3 * x * 1024),
+ *                      X0[y] = cvRound((M1 * y + M2) * 1024) + round_delta, Y0[y] likewise with M4, M5; round_delta 512 (nearest) or 16
+ *                      (linear). Sums wrap; every index derived from a table is range-tested: a wrong table gives zeros or wrong pixels.
+ *   mg_affine_warp_planes     : INTER_NEAREST, BORDER_CONSTANT 0, in / out uint8 [planes][H][W]: out(y, x) = in(sy, sx), sx = (X0[y] +
+ *                      adelta[x]) >> 10, sy = (Y0[y] + bdelta[x]) >> 10 (arithmetic shifts), 0 when the tap is outside.
+ *   mg_affine_warp_frames     : INTER_LINEAR, BORDER_CONSTANT 0, in / out uint8 [frames][H][W][3]: X = (X0[y] + adelta[x]) >> 5, sx = X >> 5,
+ *                      fx = X & 31 (y likewise); out = (sum of the four taps times 32 * (32 - fx) * (32 - fy) ... + 16384) >> 15, each tap
+ *                      outside the image 0 on its own. minmax int32 [frames][2]: each output frame's min and max over pixels and channels
+ *                      (integer atomics; the entry initialises the words on the stream first).
+ *                      regime MG_AFFINE_STAGED: a MG_AFFINE_TILE_ROWS x MG_AFFINE_TILE_COLS output tile copies its source box (from the
+ *                      table values at the tile's corners, cut to the image) into LDS when it fits MG_AFFINE_BOX_BYTES and reads its taps
+ *                      there; other taps and larger boxes read global memory. MG_AFFINE_DIRECT: four global taps per pixel. Same bits.
+ *   mg_affine_shift_normalize : in uint8 [frames][H][W][3] -> out fp32 [frames][3][H][W] = ((float)clamp((double)v + *intensity, min, max) /
+ *                      255 - mean[c]) / std[c] with min / max = minmax[frame] (channel_shift in float64, ToTensor's .float(), Normalize).
+ *                      intensity: DEVICE double.
+ * Each returns -2 for an argument error (before any launch; H, W <= MG_AFFINE_MAX_SIDE as in OpenCV's fixed-point path), -3 when the launch
+ * would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_AFFINE_STAGED 0
+#define MG_AFFINE_DIRECT 1
+#define MG_AFFINE_TILE_ROWS 32
+#define MG_AFFINE_TILE_COLS 64
+#define MG_AFFINE_BOX_BYTES 16384
+#define MG_AFFINE_MAX_SIDE 32767
+int mg_affine_warp_planes(const uint8_t* in, uint8_t* out, const int32_t* tab, long planes, int H, int W, void* stream);
+int mg_affine_warp_frames(const uint8_t* in, uint8_t* out, const int32_t* tab, int32_t* minmax, long frames, int H, int W, int regime,
+                          void* stream);
+int mg_affine_shift_normalize(const uint8_t* in, float* out, const int32_t* minmax, const double* intensity, long frames, int H, int W,
+                              const float* mean3, const float* std3, void* stream);
+int mg_affine_limits(int* tile_rows, int* tile_cols, int* box_bytes, int* max_side);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

@@ -138,6 +138,30 @@ class DevicePreprocessor:
             m = a
         return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
 
+    def train_item_affine(self, frames_u8, alphas_u8, masks_u8, crop_draws, affine_draws, slot_ids=None, *, transition=None, mask_draws=None,
+                          lut=None, warp_masks=False):
+        """`train_item` with the loaders' RandomAffine (him.py:49, vim.py:55; utils/affine.py) between the crop and the mask chain.
+        `affine_draws`: an affine.AffineDraws made for the cropped size (`affine.draw`), or None. None, or draws that did not fire (90 % of
+        the items), give `train_item` itself, bit for bit. Fired draws take the raw uint8 crop (with `lut`), the warp of frames and alphas, the
+        channel shift and Normalize; 'alpha' and `transition` come from the warped alphas. The reference does not warp the masks: with
+        `warp_masks=False` (the image loader, him.py:49-57) the mask chain reads the UNWARPED cropped masks, also when `masks_u8 is alphas_u8`;
+        `warp_masks=True` (the video loader, which regenerates the masks from the alphas afterwards, vim.py:55-59) hands it the warped alphas."""
+        from . import affine, crop
+        if affine_draws is not None and not isinstance(affine_draws, affine.AffineDraws):
+            raise TypeError('affine_draws must be an affine.AffineDraws or None (got %s)' % type(affine_draws).__name__)
+        if affine_draws is None or not affine_draws.fired:
+            return self.train_item(frames_u8, alphas_u8, masks_u8, crop_draws, slot_ids, transition=transition, mask_draws=mask_draws, lut=lut)
+        if len(frames_u8.shape) != 4:
+            raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
+        f, a, m = crop.apply(frames_u8, alphas_u8, None if (masks_u8 is alphas_u8 or warp_masks) else masks_u8, crop_draws, normalize=False,
+                             lut=lut, device=self.device)
+        if masks_u8 is alphas_u8 and not warp_masks:
+            m = a
+        image, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
+        if warp_masks and masks_u8 is not None:
+            m = a
+        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
+
     def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):
         """The evaluation item of him.py:151-202 / vim.py:150-209 from decoded files: (T, h, w, 3) uint8 frames (a clip of T equal-sized
         frames in one call; (h, w, 3) is T = 1), (T, n_i, h, w) `ori_alphas`, optionally (T, n_i, h, w) guidance masks of a mask directory.

@@ -1383,7 +1383,7 @@ extern "C" int mg_bn_train_fwd(const mg_rowwise_params* p_in, float* stats_ws, i
         if (p.M > 0) { rc = mg_colstats_centered_dev(p.x, p.dtype, p.M, C, p.ldx, own, 0, p.m_dev, stream); if (rc) return rc; }
         if (bn_fused_ok(p) && p.y) return bn_apply_fused_launch(p, own, 1, 1, gamma, beta, running_mean, running_var, momentum, eps, outs, st);
         rc = bn_finalize_launch(own, 1, nullptr, (float)p.M, C, 1, gamma, beta, running_mean, running_var, momentum, eps, outs, outs + C, outs + 2 * C,
-                                outs + 3 * C, p.m_dev, stream);
+                                outs + 3 * C, p.m_dev, stream, p.count_mult);
         if (rc) return rc;
         p.scale = outs; p.shift = outs + C;
         return p.y ? mg_affine_act(&p, stream) : 0;          // (y == NULL: the consumer applies scale | shift to its operand, mg_conv_params.xf_*)

@@ -711,6 +711,39 @@ int mg_affine_shift_normalize(const uint8_t* in, float* out, const int32_t* minm
 int mg_affine_limits(int* tile_rows, int* tile_cols, int* box_bytes, int* max_side);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * The photometric steps of the training stream on the device (csrc/photometric.hip; maggie/dataloader/transforms.py:812-924, him.py:46-48,
+ * vim.py:51-54): a per-channel tone curve, additive noise, and the JPEG round trip of JpegCompression -- the lossy part of libjpeg-turbo at
+ * Pillow's defaults (baseline, 4:2:0, JDCT_ISLOW, fancy upsampling) without the lossless entropy coding. uint8 in, int32 arithmetic: bit-exact.
+ * Every table is a DEVICE buffer, so a captured launch follows values written between replays.
+ *   lut              : uint8 [3][256] or NULL: channel c of a pixel becomes lut[c][v], first.
+ *   noise            : int16 [h][w][noise_channels] or NULL, noise_channels 1 (one sample per pixel) or 3: v = clamp(v + noise, 0, 255), after
+ *                      `lut`; the same plane for every frame.
+ *   qtab             : int32 [2][64], the luma and chroma quantisation tables in natural order, 1..255 (other values are clamped to that).
+ *   mg_jpeg_ycc      : in uint8 [frames][h][w][3] -> `planes`: the DECODED component planes Y uint8 [frames][h16][w16], then Cb, then Cr
+ *                      [frames][h16 / 2][w16 / 2] (h16, w16 = h, w rounded up to 16; frames * h16 * w16 * 3 / 2 bytes, 16-byte aligned): lut,
+ *                      noise, RGB -> YCbCr, the encoder's edge replication, h2v2 downsampling, forward DCT, quantisation, dequantisation,
+ *                      inverse DCT, clamp. A workgroup of MG_JPEG_THREADS lanes owns a MG_JPEG_TILE_ROWS x MG_JPEG_TILE_COLS tile of MCUs.
+ *   mg_jpeg_rgb      : `planes` -> out: triangle upsampling of Cb / Cr over the real ceil(h / 2) x ceil(w / 2) samples (2 x 2 replication
+ *                      when ceil(w / 2) <= 2), YCbCr -> RGB, clamp. epilogue MG_PHOTO_RAW: out uint8 [frames][h][w][3]; MG_PHOTO_NORM: out fp32
+ *                      [frames][3][h][w] = (v / 255 - mean[c]) / std[c], the bits of mg_preprocess_image on the raw result. A lane owns 16
+ *                      pixels of a row: 16-byte stores when w is a multiple of 16 and `out` is 16-byte aligned, per element otherwise.
+ *   mg_photo_noise   : `lut` and / or `noise` alone (either may be NULL), in uint8 [frames][h][w][3] -> out with the same two epilogues.
+ * Each returns -2 for an argument error (before any launch; h, w <= MG_JPEG_MAX_SIDE), -3 when the launch would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_PHOTO_RAW 0
+#define MG_PHOTO_NORM 1
+#define MG_JPEG_TILE_ROWS 32
+#define MG_JPEG_TILE_COLS 64
+#define MG_JPEG_THREADS 384
+#define MG_JPEG_MAX_SIDE 32767
+int mg_jpeg_ycc(const uint8_t* in, uint8_t* planes, const uint8_t* lut, const int16_t* noise, int noise_channels, const int32_t* qtab, long frames,
+                int h, int w, void* stream);
+int mg_jpeg_rgb(const uint8_t* planes, void* out, long frames, int h, int w, int epilogue, const float* mean3, const float* std3, void* stream);
+int mg_photo_noise(const uint8_t* in, void* out, const uint8_t* lut, const int16_t* noise, int noise_channels, long frames, int h, int w,
+                   int epilogue, const float* mean3, const float* std3, void* stream);
+int mg_jpeg_limits(int* tile_rows, int* tile_cols, int* threads, int* max_side);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

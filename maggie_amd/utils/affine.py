@@ -17,7 +17,8 @@ one a given wheel takes is not checked here. Everything on the device is integer
 Normalize: bit-exact, no tolerance anywhere. An `AffineDraws` moved to the device (`.to(device)`) makes `apply` upload nothing and never
 synchronise, so it can be captured in a graph and new tables and a new intensity written into `linear`, `nearest` and `shift` between replays.
 
-The masks are not warped (the reference leaves them alone; `DevicePreprocessor.train_item_affine` has the two loaders' wirings), and `ignore_regions`,
+The bracketed steps in front of it have device forms of their own (the tone curve as `lut` of utils/crop.py, noise and JPEG in
+utils/photometric.py; `DevicePreprocessor.train_item_photo` runs them between the crop and this warp). The masks are not warped (the reference leaves them alone; `DevicePreprocessor.train_item_affine` has the two loaders' wirings), and `ignore_regions`,
 which the reference writes and nobody reads, is not produced. Wrong dtype, rank or size raise before a launch. There is no CPU fallback."""
 import numpy as np
 import torch

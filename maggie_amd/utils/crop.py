@@ -14,10 +14,11 @@ tables of the padding branch are `geometry.resize_tables` on the padded size (`m
 `CropDraws` moved to the device (`.to(device)`) makes `apply` upload nothing and never synchronise, so it can be captured in a graph and a new
 window written into `draws.window` between replays.
 
-What stays with the caller: the `rand()` draws of GammaContrast, AdditiveGaussionNoise, JpegCompression, RandomAffine (and MotionBlur for video),
-which follow the flip in the reference's stream and precede the mask chain's, and those augmentations themselves (`lut` is the device form of a
-per-channel tone curve the caller drew; no equality with imgaug is claimed, its draws come from its own generator); the `> 127` area filter and
-the random instance removal of him.py:119-149.
+What stays with the caller: the draws of GammaContrast, AdditiveGaussionNoise and JpegCompression (imgaug's own generators; no equality with
+them is claimed), which follow the flip in the reference's stream and precede the mask chain's, and MotionBlur for video. The steps
+themselves have device forms: `lut` here is a per-channel tone curve the caller drew, utils/photometric.py has the noise and the JPEG round
+trip, utils/affine.py RandomAffine with its draws. Also the caller's: the `> 127` area filter and the random instance removal of
+him.py:119-149.
 
 Wrong dtype, rank or size raise before a launch; a crop larger than the image raises the reference's ValueError. There is no CPU fallback."""
 import numpy as np

@@ -162,6 +162,47 @@ class DevicePreprocessor:
             m = a
         return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
 
+    def train_item_photo(self, frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws=None, slot_ids=None, *, transition=None,
+                         mask_draws=None, lut=None, warp_masks=False):
+        """`train_item` / `train_item_affine` with the photometric steps that follow the flip in the reference's stream (GammaContrast,
+        AdditiveGaussionNoise, JpegCompression: him.py:46-48, vim.py:51-54; utils/photometric.py) between the crop and RandomAffine.
+        `photo`: a photometric.PhotoDraws made for the cropped size, or None; `affine_draws`: as in `train_item_affine`, or None.
+        None, or draws with neither noise nor quality, give `train_item_affine` itself, bit for bit and through its code path; a `photo.lut`
+        then joins the crop's table, after `lut`, and the crop's own Normalize epilogue stays in use. Otherwise the raw uint8 crop (with `lut`)
+        feeds `photometric.apply` (`photo.lut`, the noise, the JPEG round trip): with its Normalize epilogue when no affine fires, raw when
+        one does, because the warp reads uint8. Alphas and masks are untouched, as in the reference (the alpha line of JpegCompression is
+        commented out). `train_item` and `train_item_affine` keep their signatures; this wiring is a method of its own, as the affine one is."""
+        from . import affine, crop, photometric
+        if photo is not None and not isinstance(photo, photometric.PhotoDraws):
+            raise TypeError('photo must be a photometric.PhotoDraws or None (got %s)' % type(photo).__name__)
+        if affine_draws is not None and not isinstance(affine_draws, affine.AffineDraws):
+            raise TypeError('affine_draws must be an affine.AffineDraws or None (got %s)' % type(affine_draws).__name__)
+        if photo is None or not photo.fired:
+            if photo is not None and photo.lut is not None:
+                lut = photo.lut if lut is None else photometric.compose_luts(lut, photo.lut, self._device_of(frames_u8))
+            return self.train_item_affine(frames_u8, alphas_u8, masks_u8, crop_draws, affine_draws, slot_ids, transition=transition,
+                                          mask_draws=mask_draws, lut=lut, warp_masks=warp_masks)
+        if len(frames_u8.shape) != 4:
+            raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
+        warped = affine_draws is not None and affine_draws.fired
+        f, a, m = crop.apply(frames_u8, alphas_u8, None if (masks_u8 is alphas_u8 or (warped and warp_masks)) else masks_u8, crop_draws,
+                             normalize=False, lut=lut, device=self.device)
+        if masks_u8 is alphas_u8 and not (warped and warp_masks):
+            m = a
+        if not warped:
+            image = photometric.apply(f, photo, normalize=True, mean=self.mean, std=self.std, device=self.device)
+        else:
+            f = photometric.apply(f, photo, normalize=False, device=self.device)
+            image, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
+            if warp_masks and masks_u8 is not None:
+                m = a
+        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
+
+    def _device_of(self, x):
+        if self.device is not None:
+            return torch.device(self.device)
+        return x.device if torch.is_tensor(x) and x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+
     def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):
         """The evaluation item of him.py:151-202 / vim.py:150-209 from decoded files: (T, h, w, 3) uint8 frames (a clip of T equal-sized
         frames in one call; (h, w, 3) is T = 1), (T, n_i, h, w) `ori_alphas`, optionally (T, n_i, h, w) guidance masks of a mask directory.

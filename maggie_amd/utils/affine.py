@@ -26,7 +26,7 @@ import torch
 from .. import hip
 from ..hip import c_int, c_long
 from . import geometry
-from .preprocess import IMAGENET_MEAN, IMAGENET_STD
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, images, int_table, integer, resolve_device, to_device, upload
 
 LINEAR, NEAREST = geometry.LINEAR, geometry.NEAREST
 STAGED, DIRECT = 0, 1                      # MG_AFFINE_STAGED / MG_AFFINE_DIRECT (include/maggie_hip.h)
@@ -120,22 +120,13 @@ class AffineDraws:
         return split(self.linear if interp == LINEAR else self.nearest, self.H, self.W)
 
     def to(self, device=None):
-        if not torch.cuda.is_available():
-            raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU; there is no CPU fallback')
-        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-
-        def up(a):
-            if a is None:
-                return None
-            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device, non_blocking=True)
-        return AffineDraws(self.fired, self.H, self.W, self.matrix, self.intensity, self.form, up(self.linear), up(self.nearest), up(self.shift),
-                           self.staged_ok)
+        device = resolve_device(device)
+        return AffineDraws(self.fired, self.H, self.W, self.matrix, self.intensity, self.form, upload(self.linear, device),
+                           upload(self.nearest, device), upload(self.shift, device), self.staged_ok)
 
 
 def _size(H, W):
-    H, W = geometry._int(H, 'H'), geometry._int(W, 'W')
+    H, W = integer(H, 'H'), integer(W, 'W')
     if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
         raise ValueError('the arrays must be 1..%d pixels a side (got %d x %d)' % (MAX_SIDE, H, W))
     return H, W
@@ -217,29 +208,24 @@ def _check(frames_u8, alphas_u8, draws, regime):
         raise TypeError('draws must be an AffineDraws (got %s)' % type(draws).__name__)
     if not draws.fired:
         raise ValueError('the draws did not fire: the item takes the path without RandomAffine')
-    f, flead, fn, H, W = geometry._images(frames_u8, 3, 'frames')
+    f, flead, fn, H, W = images(frames_u8, 3, 'frames')
     if (H, W) != (draws.H, draws.W):
         raise ValueError('the draws were made for %d x %d arrays (got frames of %d x %d)' % (draws.H, draws.W, H, W))
     a = None
     if alphas_u8 is not None:
-        x, lead, n, h, w = geometry._images(alphas_u8, 1, 'alphas')
+        x, lead, n, h, w = images(alphas_u8, 1, 'alphas')
         if (h, w) != (H, W):
             raise ValueError('alphas: expected %d x %d like the frames (got %d x %d)' % (H, W, h, w))
         a = (x, lead, n)
     return f, flead, fn, H, W, a, _regime(draws, regime, fn)
 
 
-def _table(t, device, n, what):
-    from .crop import _table as crop_table
-    return crop_table(t, device, n, what)
-
-
 def _warp(frames_u8, alphas_u8, draws, regime, device):
     f, flead, fn, H, W, a, regime = _check(frames_u8, alphas_u8, draws, regime)
-    f = geometry._to_device(f, device)
+    f = to_device(f, device)
     dev = f.device
     n = 2 * (H + W)
-    linear = _table(draws.linear, dev, n, 'AffineDraws.linear')
+    linear = int_table(draws.linear, dev, n, 'AffineDraws.linear')
     out_f = torch.empty((fn, H, W, 3), dtype=torch.uint8, device=dev)
     mm = torch.empty((fn, 2), dtype=torch.int32, device=dev)
     if fn > 0:
@@ -248,8 +234,8 @@ def _warp(frames_u8, alphas_u8, draws, regime, device):
     out_a = None
     if a is not None:
         x, lead, pn = a
-        x = geometry._to_device(x, dev)
-        nearest = _table(draws.nearest, dev, n, 'AffineDraws.nearest')
+        x = to_device(x, dev)
+        nearest = int_table(draws.nearest, dev, n, 'AffineDraws.nearest')
         out_a = torch.empty((pn, H, W), dtype=torch.uint8, device=dev)
         if pn > 0:
             hip.call('mg_affine_warp_planes', hip.ptr(x), hip.ptr(out_a), hip.ptr(nearest), c_long(pn), c_int(H), c_int(W), hip.stream())
@@ -271,10 +257,10 @@ def warp(frames_u8, alphas_u8, draws, *, regime=None, return_minmax=False, devic
 def shift_normalize(frames_u8, minmax, shift, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
     """channel_shift + ToTensor + Normalize of (..., H, W, 3) uint8 frames: ((float)clip(v + shift, min, max) / 255 - mean) / std with the
     add and the clip in float64. `minmax`: int32 (T, 2) per frame; `shift`: a float, or float64 [1] on the device. -> (..., 3, H, W) fp32."""
-    f, flead, fn, H, W = geometry._images(frames_u8, 3, 'frames')
-    f = geometry._to_device(f, device)
+    f, flead, fn, H, W = images(frames_u8, 3, 'frames')
+    f = to_device(f, device)
     dev = f.device
-    mm = _table(minmax, dev, 2 * fn, 'minmax')
+    mm = int_table(minmax, dev, 2 * fn, 'minmax')
     if torch.is_tensor(shift):
         if shift.dtype != torch.float64 or shift.numel() != 1:
             raise ValueError('shift must be one float64 (got %s %s)' % (shift.dtype, tuple(shift.shape)))
@@ -284,7 +270,7 @@ def shift_normalize(frames_u8, minmax, shift, mean=IMAGENET_MEAN, std=IMAGENET_S
     out = torch.empty((fn, 3, H, W), dtype=torch.float32, device=dev)
     if fn > 0:
         hip.call('mg_affine_shift_normalize', hip.ptr(f), hip.ptr(out), hip.ptr(mm), hip.ptr(shift), c_long(fn), c_int(H), c_int(W),
-                 (hip.ctypes.c_float * 3)(*mean), (hip.ctypes.c_float * 3)(*std), hip.stream())
+                 float3(mean), float3(std), hip.stream())
     return out.reshape(flead + (3, H, W))
 
 

@@ -27,9 +27,8 @@ import torch
 from .. import hip
 from ..hip import c_int, c_long
 from . import geometry
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, images, int_table, integer, lut_table, resolve_device, to_device, upload
 from .geometry import LINEAR, NEAREST
-from .groundtruth import _check_u8
-from .preprocess import IMAGENET_MEAN, IMAGENET_STD, normalize_frames
 
 RAW, NORM = 0, 1                           # MG_CROP_RAW / MG_CROP_NORM (include/maggie_hip.h)
 MAX_WINDOWS = 3                            # MG_CROP_MAX_WINDOWS: the reference tries three windows
@@ -46,7 +45,7 @@ def _size(crop_size):
         ch, cw = crop_size
     except (TypeError, ValueError):
         raise TypeError('crop_size must be (height, width) (got %r)' % (crop_size,))
-    return geometry._int(ch, 'crop_size'), geometry._int(cw, 'crop_size')
+    return integer(ch, 'crop_size'), integer(cw, 'crop_size')
 
 
 def pad_amounts(H, W):
@@ -89,18 +88,9 @@ class CropDraws:
         return torch.is_tensor(self.window if self.branch == 'crop' else self.linear)
 
     def to(self, device=None):
-        if not torch.cuda.is_available():
-            raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU; there is no CPU fallback')
-        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-
-        def up(a):
-            if a is None:
-                return None
-            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device, non_blocking=True)
-        return CropDraws(self.branch, self.H, self.W, self.crop_size, self.flip, self.out_h, self.out_w, up(self.window), self.pairs, self.box,
-                         self.pad, up(self.linear), up(self.nearest))
+        device = resolve_device(device)
+        return CropDraws(self.branch, self.H, self.W, self.crop_size, self.flip, self.out_h, self.out_w, upload(self.window, device), self.pairs,
+                         self.box, self.pad, upload(self.linear, device), upload(self.nearest, device))
 
 
 def draw(random, H, W, crop_size, padding_prob, flip_p, bbox, hits):
@@ -113,7 +103,7 @@ def draw(random, H, W, crop_size, padding_prob, flip_p, bbox, hits):
     all three candidates are drawn from a saved state, `hits` answers for them at once, and the consumed pairs are replayed from that state: one
     question instead of up to three, the same generator state afterwards. An empty box is the reference's `except`: (0, W, 0, H) -- W, not
     W - 1."""
-    H, W = geometry._int(H, 'H'), geometry._int(W, 'W')
+    H, W = integer(H, 'H'), integer(W, 'W')
     ch, cw = _size(crop_size)
     if H < ch or W < cw:
         raise ValueError('Crop size {} is larger than image size {}'.format(crop_size, (H, W)))       # transforms.py:231
@@ -146,8 +136,7 @@ def draw(random, H, W, crop_size, padding_prob, flip_p, bbox, hits):
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------------------------
 def _planes(x_u8, what):
-    x, lead, n, H, W = geometry._images(x_u8, 1, what)
-    return x, lead, n, H, W
+    return images(x_u8, 1, what)
 
 
 def bbox(alphas_u8, device=None):
@@ -156,7 +145,7 @@ def bbox(alphas_u8, device=None):
     x, _, P, H, W = _planes(alphas_u8, 'alphas')
     if P < 1 or P > MAX_PLANES:
         raise ValueError('expected 1..%d planes (got %d)' % (MAX_PLANES, P))
-    x = geometry._to_device(x, device)
+    x = to_device(x, device)
     out = torch.empty((5,), dtype=torch.int32, device=x.device)
     hip.call('mg_crop_bbox', hip.ptr(x), hip.ptr(out), c_long(P), c_int(H), c_int(W), hip.stream())
     return out
@@ -179,7 +168,7 @@ def window_hits(alphas_u8, windows, crop_size, device=None):
         n = windows.shape[0]
     if n > MAX_WINDOWS:
         raise ValueError('at most %d windows (got %d)' % (MAX_WINDOWS, n))
-    x = geometry._to_device(x, device)
+    x = to_device(x, device)
     wt = windows.contiguous() if torch.is_tensor(windows) else torch.from_numpy(windows).to(x.device, non_blocking=True)
     hip.need_cuda(wt)
     out = torch.zeros((n,), dtype=torch.int32, device=x.device)
@@ -200,7 +189,7 @@ def draw_on_device(random, alphas_u8, crop_size, padding_prob=0.5, flip_p=0.5, d
 
     def on_device():
         if not held:
-            held.append(geometry._to_device(x, device))
+            held.append(to_device(x, device))
         return held[0]
 
     def box():
@@ -212,36 +201,6 @@ def draw_on_device(random, alphas_u8, crop_size, padding_prob=0.5, flip_p=0.5, d
     return draw(random, H, W, crop_size, padding_prob, flip_p, box, first_hit)
 
 
-def _lut(lut, device):
-    if lut is None:
-        return None
-    if torch.is_tensor(lut):
-        if lut.dtype != torch.uint8 or tuple(lut.shape) != (3, 256):
-            raise ValueError('lut must be uint8 of shape (3, 256) (got %s %s)' % (lut.dtype, tuple(lut.shape)))
-        return lut.to(device, non_blocking=True).contiguous()
-    a = np.asarray(lut)
-    if a.dtype != np.uint8 or a.shape != (3, 256):
-        raise ValueError('lut must be uint8 of shape (3, 256) (got %s %s)' % (a.dtype, a.shape))
-    return torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
-
-
-def _table(t, device, n, what):
-    """A draw table as a contiguous device int32 tensor of n entries (uploaded when it is an array)."""
-    if torch.is_tensor(t):
-        if t.dtype != torch.int32 or t.numel() != n:
-            raise ValueError('%s must be int32 with %d entries (got %s %s)' % (what, n, t.dtype, tuple(t.shape)))
-        hip.need_cuda(t)
-        return t.contiguous()
-    a = np.asarray(t)
-    if a.size != n or not np.issubdtype(a.dtype, np.integer):
-        raise ValueError('%s must hold %d ints (got %s %s)' % (what, n, a.dtype, a.shape))
-    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(device, non_blocking=True)
-
-
-def _floats(v):
-    return (hip.ctypes.c_float * 3)(*v)
-
-
 def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
     """The crop (or pad-and-resize) and the flip of `draws` on the stacked uint8 arrays of one item: frames (T, H, W, 3), alphas (P, H, W),
     masks (P, H, W) or None (any leading dimensions). Returns (frames, alphas, masks) on the device: uint8 in the input layout at
@@ -250,7 +209,7 @@ def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, m
     alphas of the padding branch are INTER_LINEAR, masks INTER_NEAREST; a tap in the border reads 0."""
     if not isinstance(draws, CropDraws):
         raise TypeError('draws must be a CropDraws (got %s)' % type(draws).__name__)
-    f, flead, fn, H, W = geometry._images(frames_u8, 3, 'frames')
+    f, flead, fn, H, W = images(frames_u8, 3, 'frames')
     if (H, W) != (draws.H, draws.W):
         raise ValueError('the draws were made for %d x %d arrays (got frames of %d x %d)' % (draws.H, draws.W, H, W))
     planes = []
@@ -262,15 +221,14 @@ def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, m
         if (h, w) != (H, W):
             raise ValueError('%s: expected %d x %d like the frames (got %d x %d)' % (what, H, W, h, w))
         planes.append((x, lead, n))
-    if lut is not None and not torch.is_tensor(lut):
-        _lut(lut, 'cpu')                                                       # the shape and dtype errors, before the device
-    f = geometry._to_device(f, device)
+    lut_table(lut)                                                             # the shape and dtype errors, before the device
+    f = to_device(f, device)
     dev = f.device
-    lut = _lut(lut, dev)
+    lut = lut_table(lut, dev)
     oh, ow = draws.out_h, draws.out_w
-    m3, s3 = _floats(mean), _floats(std)
+    m3, s3 = float3(mean), float3(std)
     if draws.branch == 'crop':
-        window = _table(draws.window, dev, 3, 'CropDraws.window')
+        window = int_table(draws.window, dev, 3, 'CropDraws.window')
 
         def run(x, n, C, epilogue, table):
             shape = (n, 3, oh, ow) if epilogue == NORM else (n, oh, ow) + ((3,) if C == 3 else ())
@@ -280,8 +238,8 @@ def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, m
                          c_int(oh), c_int(ow), c_int(epilogue), m3, s3, hip.stream())
             return out
     else:
-        linear = _table(draws.linear, dev, 3 * (ow + oh), 'CropDraws.linear')
-        nearest = _table(draws.nearest, dev, ow + oh, 'CropDraws.nearest')
+        linear = int_table(draws.linear, dev, 3 * (ow + oh), 'CropDraws.linear')
+        nearest = int_table(draws.nearest, dev, ow + oh, 'CropDraws.nearest')
         pad_h, pad_w = draws.pad
 
         def run(x, n, C, epilogue, table, interp=LINEAR):
@@ -297,6 +255,7 @@ def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, m
     else:
         out_f = run(f, fn, 3, RAW, lut).reshape(flead + (oh, ow, 3))
         if normalize:
+            from .preprocess import normalize_frames       # lazy: preprocess imports this module for the training item's wiring
             out_f = normalize_frames(out_f, mean, std, dev)
     outs = [out_f]
     for entry, interp in zip(planes, (LINEAR, NEAREST)):
@@ -304,7 +263,7 @@ def apply(frames_u8, alphas_u8, masks_u8, draws, *, normalize=False, lut=None, m
             outs.append(None)
             continue
         x, lead, n = entry
-        x = geometry._to_device(x, dev)
+        x = to_device(x, dev)
         o = run(x, n, 1, RAW, None) if draws.branch == 'crop' else run(x, n, 1, RAW, None, interp)
         outs.append(o.reshape(lead + (oh, ow)))
     return outs[0], outs[1], outs[2]

@@ -23,9 +23,8 @@ import torch
 
 from .. import hip
 from ..hip import c_int, c_long
-from .groundtruth import _check_u8, _need_gpu
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, check_u8, float3, images, integer, to_device
 from .maskgen import resize_axis
-from .preprocess import IMAGENET_MEAN, IMAGENET_STD
 
 LINEAR, NEAREST = 0, 1                     # MG_RESIZE_LINEAR / MG_RESIZE_NEAREST (include/maggie_hip.h)
 RAW, NORM, SLOTS = 0, 1, 2                 # MG_RESIZE_RAW / _NORM / _SLOTS
@@ -40,12 +39,6 @@ _DEVICE_MASK8 = {}                         # (plan key, device index) -> the com
 
 
 # ---- the host side ------------------------------------------------------------------------------------------------------------------------------
-def _int(v, what):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-        raise TypeError('%s must be an int (got %r)' % (what, v))
-    return int(v)
-
-
 def nearest_axis(src, dst):
     """One axis of cv2.resize(INTER_NEAREST) (the legacy rule, not INTER_NEAREST_EXACT): min(floor(d * (1.0 / (dst / src))), src - 1), in double."""
     ifx = 1.0 / (np.float64(dst) / np.float64(src))
@@ -65,7 +58,7 @@ def resize_tables(H, W, dh, dw):
     """The tables of cv2.resize from (H, W) to (dh, dw), cached: `x`, `y` the linear axes (ofs, c0, c1) with scale 1.0 / (dst / src);
     `nx`, `ny` the nearest indices; `linear` ([dw][3] | [dh][3]) and `nearest` ([dw] | [dh]) the int32 buffers the kernel reads;
     `rows_read` the worst tile's source-row footprint and `regime` the kernel form the host picks from it."""
-    H, W, dh, dw = _int(H, 'H'), _int(W, 'W'), _int(dh, 'dh'), _int(dw, 'dw')
+    H, W, dh, dw = integer(H, 'H'), integer(W, 'W'), integer(dh, 'dh'), integer(dw, 'dw')
     key = (H, W, dh, dw)
     if key in _TABLES:
         return _TABLES[key]
@@ -141,7 +134,7 @@ class Plan:
 
 def plan(h, w, short_size, divisor=64):
     """The `Plan` of (h, w) sources, cached. Pure host code: usable without a GPU."""
-    h, w, short_size, divisor = _int(h, 'h'), _int(w, 'w'), _int(short_size, 'short_size'), _int(divisor, 'divisor')
+    h, w, short_size, divisor = integer(h, 'h'), integer(w, 'w'), integer(short_size, 'short_size'), integer(divisor, 'divisor')
     if h < 1 or w < 1:
         raise ValueError('the source must have at least one pixel (got %d x %d)' % (h, w))
     if short_size < 1:
@@ -163,36 +156,9 @@ def _device_tables(H, W, dh, dw, device):
     return _DEVICE_TABLES[key]
 
 
-def _images(x_u8, channels, what):
-    """uint8 (..., H, W) planes (channels 1) or (..., H, W, 3) frames (channels 3) -> the tensor, its leading shape, N, H, W."""
-    x = _check_u8(x_u8)
-    need = 2 if channels == 1 else 3
-    if x.dim() < need:
-        raise ValueError('%s: expected %s (got shape %s)' % (what, '(..., H, W)' if channels == 1 else '(..., H, W, 3)', tuple(x.shape)))
-    if channels == 3 and x.shape[-1] != 3:
-        raise ValueError('%s: frames must have 3 channels (got shape %s)' % (what, tuple(x.shape)))
-    lead = tuple(x.shape[:-need])
-    H, W = (int(v) for v in x.shape[-need:][:2])
-    if H < 1 or W < 1:
-        raise ValueError('%s: the source must have at least one pixel (got %d x %d)' % (what, H, W))
-    return x, lead, int(np.prod(lead)) if lead else 1, H, W
-
-
-def _to_device(x, device):
-    _need_gpu(x)
-    if device is None:
-        device = x.device if x.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type == 'cuda' and device.index is None:
-        device = torch.device('cuda', torch.cuda.current_device())
-    x = x.to(device, non_blocking=True).contiguous()
-    hip.need_cuda(x)
-    return x
-
-
 def _launch(x, out, xtab, ytab, slots, images, n_in, n_slots, C, H, W, dh, dw, Ho, Wo, interp, epilogue, regime, mean=None, std=None, thresh=0):
-    m = None if mean is None else (hip.ctypes.c_float * 3)(*mean)
-    s = None if std is None else (hip.ctypes.c_float * 3)(*std)
+    m = None if mean is None else float3(mean)
+    s = None if std is None else float3(std)
     hip.call('mg_resize_u8', hip.ptr(x), hip.ptr(out), hip.ptr(xtab), hip.ptr(ytab), hip.ptr(slots), c_long(images), c_int(n_in), c_int(n_slots),
              c_int(C), c_int(H), c_int(W), c_int(dh), c_int(dw), c_int(Ho), c_int(Wo), c_int(interp), c_int(epilogue), c_int(regime), m, s,
              c_int(int(thresh)), hip.stream())
@@ -223,7 +189,7 @@ def resize(src_u8, dsize, interpolation='linear', channels=None, regime=None, de
     """cv2.resize(src, dsize, interpolation=...) of uint8 (..., H, W) planes or (..., H, W, 3) frames; `dsize` is (w, h) as in OpenCV.
     Returns a uint8 device tensor. `channels`: 1 or 3; None reads a last dimension of 3 (and a rank of at least 3) as frames.
     `regime`: None (the host picks from the tables), 'shared' or 'direct' -- the same bits from both."""
-    x = _check_u8(src_u8)
+    x = check_u8(src_u8)
     if channels is None:
         channels = 3 if x.dim() >= 3 and x.shape[-1] == 3 else 1
     if channels not in (1, 3):
@@ -233,11 +199,11 @@ def resize(src_u8, dsize, interpolation='linear', channels=None, regime=None, de
         dw, dh = dsize
     except (TypeError, ValueError):
         raise TypeError('dsize must be (w, h) (got %r)' % (dsize,))
-    dw, dh = _int(dw, 'dsize'), _int(dh, 'dsize')
-    x, lead, N, H, W = _images(x, channels, 'resize')
+    dw, dh = integer(dw, 'dsize'), integer(dh, 'dsize')
+    x, lead, N, H, W = images(x, channels, 'resize')
     t = resize_tables(H, W, dh, dw)
     rg = _regime(t, regime)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     return _raw(x, N, channels, H, W, dh, dw, dh, dw, interp, rg).reshape(lead + (dh, dw) + ((3,) if channels == 3 else ()))
 
 
@@ -255,7 +221,7 @@ def resize_short_pad(frames_u8, alphas_u8=None, masks_u8=None, short_size=768, d
     INTER_LINEAR, (..., H, W) masks with INTER_NEAREST, each padded with zeros to the right and below. Returns
     (frames, alphas, masks, transform_info): uint8 device tensors (None where nothing was given) -- the raw form, for `maskgen` or for
     inspection. With ratio == 1 nothing is resized, as in the reference."""
-    f, flead, fn, H, W = _images(frames_u8, 3, 'frames')
+    f, flead, fn, H, W = images(frames_u8, 3, 'frames')
     p = _plan_of(H, W, short_size, divisor)
     rg = _regime(p.tables, regime)
     planes = []
@@ -263,39 +229,39 @@ def resize_short_pad(frames_u8, alphas_u8=None, masks_u8=None, short_size=768, d
         if x is None:
             planes.append(None)
             continue
-        x, lead, n, h, w = _images(x, 1, what)
+        x, lead, n, h, w = images(x, 1, what)
         _check_plan(p, h, w, what)
         planes.append((x, lead, n))
-    f = _to_device(f, device)
+    f = to_device(f, device)
     out = [_raw(f, fn, 3, H, W, p.rh, p.rw, p.out_h, p.out_w, LINEAR, rg).reshape(flead + (p.out_h, p.out_w, 3))]
     for entry, interp in zip(planes, (LINEAR, NEAREST)):
         if entry is None:
             out.append(None)
             continue
         x, lead, n = entry
-        x = _to_device(x, f.device)
+        x = to_device(x, f.device)
         out.append(_raw(x, n, 1, H, W, p.rh, p.rw, p.out_h, p.out_w, interp, rg).reshape(lead + (p.out_h, p.out_w)))
     return out[0], out[1], out[2], p.transform_info
 
 
 def resize_pad_planes_u8(planes_u8, short_size=768, divisor=64, interpolation='linear', regime=None, device=None):
     """(..., H, W) uint8 planes -> (..., out_h, out_w) uint8, resized and padded like the frames of their item."""
-    x, lead, n, H, W = _images(planes_u8, 1, 'planes')
+    x, lead, n, H, W = images(planes_u8, 1, 'planes')
     p = _plan_of(H, W, short_size, divisor)
     _check_plan(p, H, W, 'planes')
     interp, rg = _interp(interpolation), _regime(p.tables, regime)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     return _raw(x, n, 1, H, W, p.rh, p.rw, p.out_h, p.out_w, interp, rg).reshape(lead + (p.out_h, p.out_w))
 
 
 def resize_pad_normalize(frames_u8, short_size=768, divisor=64, mean=IMAGENET_MEAN, std=IMAGENET_STD, regime=None, device=None):
     """(..., H, W, 3) uint8 frames -> ((..., 3, out_h, out_w) fp32, Plan): ResizeShort, PaddingMultiplyBy, ToTensor and Normalize.norm in
     one launch with no uint8 intermediate. The padding precedes Normalize in the reference, so a padded cell holds (0 / 255 - mean) / std."""
-    f, lead, n, H, W = _images(frames_u8, 3, 'frames')
+    f, lead, n, H, W = images(frames_u8, 3, 'frames')
     p = _plan_of(H, W, short_size, divisor)
     _check_plan(p, H, W, 'frames')
     rg = _regime(p.tables, regime)
-    f = _to_device(f, device)
+    f = to_device(f, device)
     xt, yt = _axes(_device_tables(H, W, p.rh, p.rw, f.device), LINEAR, p.rw)
     out = torch.empty(lead + (3, p.out_h, p.out_w), dtype=torch.float32, device=f.device)
     if n > 0:
@@ -309,7 +275,7 @@ def resize_pad_planes(planes_u8, short_size=768, divisor=64, interpolation='line
     every frame written to slot slot_ids[j] (default: identity), other slots zero -- `preprocess.scale_planes` of the planes
     `resize_short_pad` would return, in one launch. `down8` (masks, nearest only): (Ho, Wo) = (out_h // 8, out_w // 8), the nearest
     down-scale of him.py:175-176 folded into the index map; otherwise (Ho, Wo) = (out_h, out_w)."""
-    x = _check_u8(planes_u8)
+    x = check_u8(planes_u8)
     if x.dim() != 4:
         raise ValueError('expected (F, n_i, H, W) planes (got shape %s)' % (tuple(x.shape),))
     F_, n_i, H, W = (int(v) for v in x.shape)
@@ -320,7 +286,7 @@ def resize_pad_planes(planes_u8, short_size=768, divisor=64, interpolation='line
     interp, rg = _interp(interpolation), _regime(p.tables, regime)
     if down8 and interp != NEAREST:
         raise ValueError('down8 composes index maps: it needs nearest interpolation')
-    n_slots = n_i if n_slots is None else _int(n_slots, 'n_slots')
+    n_slots = n_i if n_slots is None else integer(n_slots, 'n_slots')
     src = None
     if slot_ids is not None:
         ids = [int(i) for i in slot_ids]
@@ -332,7 +298,7 @@ def resize_pad_planes(planes_u8, short_size=768, divisor=64, interpolation='line
     elif n_slots != n_i:
         raise ValueError('n_slots != n_i needs slot_ids')
     m8 = p.mask8() if down8 else None
-    x = _to_device(x, device)
+    x = to_device(x, device)
     if down8:
         Ho, Wo, vh, vw, tab = m8
         key = (p.key, x.device.index)

@@ -16,23 +16,12 @@ import torch
 
 from .. import hip
 from ..hip import c_int, c_long
+from ._inputs import check_u8, resolve_device, to_device
 
 MAX_K = 31                      # the ellipse span table of csrc/se_table.h
 MAX_HALO = 48                   # MG_MORPH_MAX_HALO (include/maggie_hip.h)
 MODE_TRANSITION, MODE_TRIMAP = 0, 1          # MG_GT_*
 _PREPARED = set()               # device indices whose span table is uploaded
-
-
-def _check_u8(x):
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.uint8:
-            raise TypeError('expected uint8 planes, got %s' % x.dtype)
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if not torch.is_tensor(x):
-        raise TypeError('expected a uint8 tensor or array, got %s' % type(x).__name__)
-    if x.dtype != torch.uint8:
-        raise TypeError('expected uint8 planes, got %s' % x.dtype)
-    return x
 
 
 def _per_frame(v, frames, what):
@@ -87,9 +76,7 @@ def draws(k_size, iterations, frames, halo=None, device=None):
     halo = need if halo is None else int(halo)
     if halo < need or halo > MAX_HALO:
         raise ValueError('halo must be in %d..%d (got %d)' % (need, MAX_HALO, halo))
-    if not torch.cuda.is_available():
-        raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU; there is no CPU fallback')
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    device = resolve_device(device)
     _prepare(device)
     return Draws(torch.from_numpy(kn).to(device), halo)
 
@@ -106,12 +93,8 @@ def _check_draws(k_size, iterations, frames):
 
 
 def _device_inputs(x, k_size, iterations, frames, device):
-    """The planes and the (k, n) table on the device."""
-    if device is None:
-        device = x.device if x.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    device = torch.device(device)
-    x = x.to(device, non_blocking=True).contiguous()
-    hip.need_cuda(x)
+    """The planes and the (k, n) table on the device; without a GPU, the error of `to_device`."""
+    x = to_device(x, device)
     if isinstance(k_size, Draws):
         hip.need_cuda(k_size.kn)
         return x, k_size.kn.contiguous(), k_size.halo
@@ -120,13 +103,8 @@ def _device_inputs(x, k_size, iterations, frames, device):
     return x, torch.from_numpy(kn).to(x.device, non_blocking=True), halo
 
 
-def _need_gpu(x):
-    if not x.is_cuda and not torch.cuda.is_available():
-        raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU (got a CPU tensor and no device); there is no CPU fallback')
-
-
 def _morph(planes_u8, k, iterations, want_dil, want_ero, device):
-    x = _check_u8(planes_u8)
+    x = check_u8(planes_u8)
     if x.dim() < 2:
         raise ValueError('expected (..., H, W) planes (got shape %s)' % (tuple(x.shape),))
     shape = tuple(x.shape)
@@ -134,7 +112,6 @@ def _morph(planes_u8, k, iterations, want_dil, want_ero, device):
     frames = shape[0] if x.dim() >= 3 else 1
     per_frame = int(np.prod(shape[1:-2])) if x.dim() > 3 else 1
     _check_draws(k, iterations, frames)
-    _need_gpu(x)
     x, kn, halo = _device_inputs(x, k, iterations, frames, device)
     dil = torch.empty(shape, dtype=torch.uint8, device=x.device) if want_dil else None
     ero = torch.empty(shape, dtype=torch.uint8, device=x.device) if want_ero else None
@@ -175,7 +152,7 @@ def _slot_table(n_i, n_slots, slot_ids, frames):
 
 
 def _frames4(alphas_u8):
-    x = _check_u8(alphas_u8)
+    x = check_u8(alphas_u8)
     if x.dim() != 4:
         raise ValueError('expected (T, n_i, H, W) planes (got shape %s)' % (tuple(x.shape),))
     return x
@@ -189,7 +166,6 @@ def transition_gt(alphas_u8, k_size=25, iterations=1, thresh=0, n_slots=None, sl
     T, n_i, H, W = x.shape
     n_slots, table = _slot_table(n_i, n_slots, slot_ids, T)
     _check_draws(k_size, iterations, T)
-    _need_gpu(x)
     x, kn, halo = _device_inputs(x, k_size, iterations, T, device)
     out = torch.empty((T, n_slots, H, W), dtype=torch.float32, device=x.device)
     if n_i == 0:
@@ -218,7 +194,6 @@ def diff_transition(alphas_u8, k_size, iterations, thresh=5, n_slots=None, diff_
     if n_slots < n_i:
         raise ValueError('n_slots (%d) must be >= the number of instances (%d)' % (n_slots, n_i))
     _check_draws(k_size, iterations, T)
-    _need_gpu(x)
     x, kn, halo = _device_inputs(x, k_size, iterations, T, device)
     out = torch.empty((T, n_slots, H, W), dtype=torch.float32, device=x.device)
     if n_i == 0:

@@ -22,7 +22,7 @@ import torch
 
 from .. import hip
 from ..hip import c_int, c_long
-from .groundtruth import _check_u8, _need_gpu
+from ._inputs import check_u8, resolve_device, to_device, upload
 
 MAX_K = 31                       # MG_MASK_MAX_K (include/maggie_hip.h)
 MAX_PATCH = 66                   # MG_MASK_MAX_PATCH: side of the small-image patch one 64-pixel tile may read
@@ -146,16 +146,9 @@ class MaskDraws:
         return torch.is_tensor(self.morph)
 
     def to(self, device=None):
-        if not torch.cuda.is_available():
-            raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU; there is no CPU fallback')
-        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        tab = _device_table(self.H, self.W, self.ratio, device)
-
-        def up(a):
-            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device, non_blocking=True)
-        return MaskDraws(self.H, self.W, self.thresh, up(self.morph), up(self.downup), up(self.cut), self.dropout, self.ratio, tab)
+        device = resolve_device(device)
+        return MaskDraws(self.H, self.W, self.thresh, upload(self.morph, device), upload(self.downup, device), upload(self.cut, device),
+                         self.dropout, self.ratio, _device_table(self.H, self.W, self.ratio, device))
 
 
 def draw_chain(random, pyrandom, n_planes, H, W, binarize_max_k=30, downscale_mask_p=0.5, dropout=False, from_alpha=False, ratio=0.125):
@@ -224,8 +217,9 @@ def draw_dropout(random, stats):
 
 # ---- the device stages ------------------------------------------------------------------------------------------------------------------------
 def _planes(planes_u8):
-    """uint8 (..., H, W) -> the tensor, its shape, and (P, H, W)."""
-    x = _check_u8(planes_u8)
+    """uint8 (..., H, W) -> the tensor, its shape, and (P, H, W). Not `_inputs.images`: an empty plane is legal here (the stages return it)
+    and the whole shape is handed back."""
+    x = check_u8(planes_u8)
     if x.dim() < 2:
         raise ValueError('expected (..., H, W) planes (got shape %s)' % (tuple(x.shape),))
     shape = tuple(x.shape)
@@ -234,14 +228,6 @@ def _planes(planes_u8):
     if H * W >= 2 ** 31:
         raise ValueError('a plane must have fewer than 2^31 pixels')
     return x, shape, P, H, W
-
-
-def _to_device(x, device):
-    if device is None:
-        device = x.device if x.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    x = x.to(torch.device(device), non_blocking=True).contiguous()
-    hip.need_cuda(x)
-    return x
 
 
 def _table(t, rows, cols, what):
@@ -291,8 +277,7 @@ def binarize_morph(planes_u8, thresh, k_dilate=1, k_erode=1, order='dilate_erode
     `k_erode`, `order` is one value or one per plane; or pass a (P, 4) int32 device tensor (`MaskDraws.morph`) as `thresh`."""
     x, shape, P, H, W = _planes(planes_u8)
     table = _table(thresh, P, (4,), 'the morph table') if torch.is_tensor(thresh) else morph_table(thresh, k_dilate, k_erode, order, P)
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     return _launch_morph(x, _up(table, x.device), P, H, W).reshape(shape)
 
 
@@ -306,8 +291,7 @@ def down_up(planes_u8, apply=True, ratio=0.125, device=None):
     if x.numel() == 0:
         return x.clone()
     t = resize_tables(H, W, ratio)
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     return _launch_downup(x, _up(apply, x.device), _device_table(H, W, ratio, x.device), t['dh'], t['dw'], P, H, W).reshape(shape)
 
 
@@ -316,8 +300,7 @@ def cut(planes_u8, rects, device=None):
     src_plane written at (dst_row, dst_col); the source is the input, so overlapping rectangles and swaps read the old values."""
     x, shape, P, H, W = _planes(planes_u8)
     rects = _table(rects, P, (8,), 'the cut table')
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     return _launch_cut(x, _up(rects, x.device), P, H, W).reshape(shape)
 
 
@@ -325,8 +308,7 @@ def stats(planes_u8, device=None):
     """(P, 5) int32 on the device: (count, xmin, xmax, ymin, ymax) of the non-zero pixels of every plane; an empty plane gives
     (0, W, -1, H, -1)."""
     x, shape, P, H, W = _planes(planes_u8)
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     out = torch.empty((P, 5), dtype=torch.int32, device=x.device)
     if P > 0:
         hip.call('mg_mask_stats', hip.ptr(x), hip.ptr(out), c_long(P), c_int(H), c_int(W), hip.stream())
@@ -347,8 +329,7 @@ def drop(planes_u8, selection, plane_stats, inplace=False, device=None):
         live = selection[selection[:, 0] >= 0, 0]
         if len(set(live.tolist())) != len(live) or (len(live) and live.max() >= P):
             raise ValueError('the drop-out entries must name distinct planes below %d' % P)
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     if not inplace or not x.is_contiguous():
         x = x.clone()
     if n > 0 and x.numel() > 0:
@@ -376,8 +357,7 @@ def synthesize(planes_u8, draws, dropout_random=None, device=None):
     if x.numel() == 0:
         return x.clone()
     t = resize_tables(H, W, draws.ratio)
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     tab = draws.tab if draws.tab is not None else _device_table(H, W, draws.ratio, x.device)
     y = _launch_morph(x, _up(morph, x.device), P, H, W)
     y = _launch_downup(y, _up(apply, x.device), tab, t['dh'], t['dw'], P, H, W)
@@ -401,8 +381,7 @@ def from_alpha(alphas_u8, down_up=True, ratio=0.125, device=None):
     if x.numel() == 0:
         return x.clone()
     t = resize_tables(H, W, ratio) if down_up else None
-    _need_gpu(x)
-    x = _to_device(x, device)
+    x = to_device(x, device)
     key = (P, x.device.index)
     if key not in _ALPHA_TABLES:
         _ALPHA_TABLES[key] = (torch.tensor([127, 1, 1, ORDER_NONE], dtype=torch.int32).repeat(P, 1).to(x.device),

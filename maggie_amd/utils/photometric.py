@@ -28,9 +28,7 @@ import torch
 
 from .. import hip
 from ..hip import c_int, c_long
-from . import geometry
-from .crop import _lut
-from .preprocess import IMAGENET_MEAN, IMAGENET_STD
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, images, integer, lut_table, resolve_device, to_device, upload
 
 RAW, NORM = 0, 1                           # MG_PHOTO_RAW / MG_PHOTO_NORM (include/maggie_hip.h)
 TILE_ROWS, TILE_COLS, THREADS, MAX_SIDE = 32, 64, 384, 32767      # MG_JPEG_TILE_ROWS / _TILE_COLS / _THREADS / _MAX_SIDE
@@ -51,7 +49,7 @@ def quality_from_compression(c):
 
 
 def _quality(quality):
-    q = geometry._int(quality, 'quality')
+    q = integer(quality, 'quality')
     if not 1 <= q <= 100:
         raise ValueError('quality must be in 1..100 (got %d)' % q)
     return q
@@ -67,14 +65,6 @@ def quant_tables(quality):
 
 def _is(a, torch_dtype, numpy_dtype):
     return a.dtype == torch_dtype if torch.is_tensor(a) else a.dtype == numpy_dtype
-
-
-def _check_lut(lut):
-    if lut is not None:
-        a = lut if torch.is_tensor(lut) else np.asarray(lut)
-        if not _is(a, torch.uint8, np.uint8) or tuple(a.shape) != (3, 256):
-            raise ValueError('lut must be uint8 of shape (3, 256) (got %s %s)' % (a.dtype, tuple(a.shape)))
-    return lut
 
 
 def _check_noise(noise):
@@ -94,7 +84,7 @@ class PhotoDraws:
     capture it in a graph and write new values into `lut`, `noise` and `qtable` between replays (the kernel clamps table entries to 1..255)."""
 
     def __init__(self, lut=None, noise=None, quality=None, qtable=None):
-        self.lut, self.noise = _check_lut(lut), _check_noise(noise)
+        self.lut, self.noise = lut_table(lut), _check_noise(noise)
         self.quality = None if quality is None else _quality(quality)
         if qtable is None and self.quality is not None:
             qtable = quant_tables(self.quality)
@@ -112,34 +102,21 @@ class PhotoDraws:
         return all(torch.is_tensor(a) for a in (self.lut, self.noise, self.qtable) if a is not None)
 
     def to(self, device=None):
-        if not torch.cuda.is_available():
-            raise hip.MaggieHipError('MaGGIe HIP kernels need a GPU; there is no CPU fallback')
-        device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-
-        def up(a):
-            if a is None:
-                return None
-            return (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(device, non_blocking=True)
-        return PhotoDraws(up(self.lut), up(self.noise), self.quality, up(self.qtable))
+        device = resolve_device(device)
+        return PhotoDraws(upload(self.lut, device), upload(self.noise, device), self.quality, upload(self.qtable, device))
 
 
 def compose_luts(first, second, device):
     """The (3, 256) uint8 table of `first` followed by `second` (either may be None), on `device`; no synchronisation."""
-    a, b = _lut(first, device), _lut(second, device)
+    a, b = lut_table(first, device), lut_table(second, device)
     if a is None or b is None:
         return b if a is None else a
     return torch.gather(b, 1, a.long())
 
 
 # ---- the device side ----------------------------------------------------------------------------------------------------------------------------
-def _floats(v):
-    return (hip.ctypes.c_float * 3)(*v)
-
-
 def _frames(frames_u8, noise):
-    f, lead, n, h, w = geometry._images(frames_u8, 3, 'frames')
+    f, lead, n, h, w = images(frames_u8, 3, 'frames')
     if h > MAX_SIDE or w > MAX_SIDE:
         raise ValueError('the frames must be at most %d pixels a side (got %d x %d)' % (MAX_SIDE, h, w))
     _check_noise(noise)
@@ -151,9 +128,7 @@ def _frames(frames_u8, noise):
 def _noise(noise, device):
     if noise is None:
         return None, 1
-    if not torch.is_tensor(noise):
-        noise = torch.from_numpy(np.ascontiguousarray(noise))
-    noise = noise.to(device, non_blocking=True).contiguous()
+    noise = upload(noise, device).contiguous()
     return noise, int(noise.shape[-1])
 
 
@@ -170,8 +145,7 @@ def _check_quality(quality):
 def _qtable(quality, device):
     """`quality` as the device (2, 64) int32 table: an int 1..100, or a table (array or tensor) that is taken as it is."""
     if _check_quality(quality):
-        t = quality if torch.is_tensor(quality) else torch.from_numpy(np.ascontiguousarray(quality))
-        return t.to(device, non_blocking=True).contiguous()
+        return upload(quality, device).contiguous()
     return torch.from_numpy(quant_tables(quality)).to(device, non_blocking=True)
 
 
@@ -188,7 +162,7 @@ def _point(f, n, h, w, lut, noise, nc, epilogue, mean, std):
     out = _out(n, h, w, epilogue, f.device)
     if n > 0:
         hip.call('mg_photo_noise', hip.ptr(f), hip.ptr(out), hip.ptr(lut), hip.ptr(noise), c_int(nc), c_long(n), c_int(h), c_int(w),
-                 c_int(epilogue), _floats(mean), _floats(std), hip.stream())
+                 c_int(epilogue), float3(mean), float3(std), hip.stream())
     return out
 
 
@@ -198,7 +172,7 @@ def _jpeg(f, n, h, w, qtable, lut, noise, nc, epilogue, mean, std):
         planes = torch.empty((plane_bytes(n, h, w),), dtype=torch.uint8, device=f.device)
         hip.call('mg_jpeg_ycc', hip.ptr(f), hip.ptr(planes), hip.ptr(lut), hip.ptr(noise), c_int(nc), hip.ptr(qtable), c_long(n), c_int(h),
                  c_int(w), hip.stream())
-        hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(n), c_int(h), c_int(w), c_int(epilogue), _floats(mean), _floats(std),
+        hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(n), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std),
                  hip.stream())
     return out
 
@@ -213,7 +187,7 @@ def add_noise(frames_u8, noise, device=None):
     if noise is None:
         raise ValueError('noise must be int16 of shape (h, w, 1) or (h, w, 3) (got None)')
     f, lead, n, h, w = _frames(frames_u8, noise)
-    f = geometry._to_device(f, device)
+    f = to_device(f, device)
     nz, nc = _noise(noise, f.device)
     return _shape(_point(f, n, h, w, None, nz, nc, RAW, IMAGENET_MEAN, IMAGENET_STD), lead, h, w, False)
 
@@ -223,11 +197,11 @@ def jpeg_roundtrip(frames_u8, quality, *, lut=None, noise=None, normalize=False,
     Returns uint8 (..., h, w, 3) on the device, or with `normalize` fp32 (..., 3, h, w): ToTensor + Normalize of the uint8 result, the bits
     of `normalize_frames` on it, with no uint8 intermediate. Two launches; the decoded component planes between them stay on the device."""
     _check_quality(quality)
-    _check_lut(lut)
+    lut_table(lut)
     f, lead, n, h, w = _frames(frames_u8, noise)
-    f = geometry._to_device(f, device)
+    f = to_device(f, device)
     nz, nc = _noise(noise, f.device)
-    out = _jpeg(f, n, h, w, _qtable(quality, f.device), _lut(lut, f.device), nz, nc, NORM if normalize else RAW, mean, std)
+    out = _jpeg(f, n, h, w, _qtable(quality, f.device), lut_table(lut, f.device), nz, nc, NORM if normalize else RAW, mean, std)
     return _shape(out, lead, h, w, normalize)
 
 
@@ -239,12 +213,12 @@ def apply(frames_u8, draws, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET
     if not isinstance(draws, PhotoDraws):
         raise TypeError('draws must be a PhotoDraws (got %s)' % type(draws).__name__)
     f, lead, n, h, w = _frames(frames_u8, draws.noise)
-    f = geometry._to_device(f, device)
+    f = to_device(f, device)
     dev = f.device
     epilogue = NORM if normalize else RAW
     if draws.quality is None and draws.noise is None and draws.lut is None and not normalize:
         return f
-    lut = _lut(draws.lut, dev)
+    lut = lut_table(draws.lut, dev)
     nz, nc = _noise(draws.noise, dev)
     if draws.quality is not None:
         out = _jpeg(f.reshape(n, h, w, 3), n, h, w, _qtable(draws.qtable, dev), lut, nz, nc, epilogue, mean, std)

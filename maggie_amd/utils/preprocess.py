@@ -14,31 +14,28 @@ import torch
 
 from .. import hip
 from ..hip import c_int, c_long
-
-IMAGENET_MEAN = (0.485, 0.456, 0.406)        # maggie/dataloader/him.py: T.Normalize(mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225])
-IMAGENET_STD = (0.229, 0.224, 0.225)
+from . import affine, crop, geometry, groundtruth, maskgen, photometric
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, check_u8, float3, resolve_device          # the two constants are this module's public names too
 
 
 def _u8(x, device):
+    """The uint8 check, then the upload to `resolve_device(device)`: a dtype error comes before the no-GPU one."""
     if isinstance(x, np.ndarray):
-        x = torch.from_numpy(np.ascontiguousarray(x))
-    if x.dtype != torch.uint8:
-        raise TypeError('expected uint8 pixels, got %s' % x.dtype)
-    return x.to(device, non_blocking=True).contiguous()
+        x = torch.from_numpy(np.ascontiguousarray(x))                 # first: the message has always named the torch dtype
+    return check_u8(x, 'pixels').to(resolve_device(device), non_blocking=True).contiguous()
 
 
 def normalize_frames(frames_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
     """(..., H, W, 3) uint8 -> (..., 3, H, W) fp32 normalised (ToTensor + Normalize.norm)."""
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     x = _u8(frames_u8, device)
     hip.need_cuda(x)
+    device = x.device
     *lead, H, W, C = x.shape
     if C != 3:
         raise ValueError('frames must be (..., H, W, 3)')
     n = int(np.prod(lead)) if lead else 1
     out = torch.empty(tuple(lead) + (3, H, W), dtype=torch.float32, device=device)
-    m = (hip.ctypes.c_float * 3)(*mean)
-    s = (hip.ctypes.c_float * 3)(*std)
+    m, s = float3(mean), float3(std)
     for f0 in range(0, n, 65535):
         f1 = min(n, f0 + 65535)
         hip.call('mg_preprocess_image', hip.ctypes.c_void_p(x.data_ptr() + f0 * H * W * 3), hip.ctypes.c_void_p(out.data_ptr() + f0 * H * W * 12),
@@ -49,9 +46,9 @@ def normalize_frames(frames_u8, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=Non
 def scale_planes(planes_u8, n_slots=None, slot_ids=None, out_size=None, thresh=0, device=None):
     """(F, n_i, H, W) uint8 -> (F, n_slots, Ho, Wo) fp32 = v / 255 (0 below `thresh`), plane j of every frame written to slot
     slot_ids[j] (default: identity, n_slots = n_i), other slots zero; (Ho, Wo) != (H, W): F.interpolate(mode='nearest')."""
-    device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     x = _u8(planes_u8, device)
     hip.need_cuda(x)
+    device = x.device
     F_, n_i, H, W = x.shape
     n_slots = n_i if n_slots is None else int(n_slots)
     Ho, Wo = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
@@ -103,13 +100,11 @@ class DevicePreprocessor:
         if masks_u8 is not None:
             m = masks_u8.reshape(T, -1, H, W)
             if mask_draws is not None:
-                from . import maskgen
                 draws, dropout_random = mask_draws if isinstance(mask_draws, tuple) else (mask_draws, None)
                 m = maskgen.synthesize(m, draws, dropout_random, device=self.device)
             size = (H // 8, W // 8) if self.downscale_mask else None                                   # him.py:172-173
             out['mask'] = scale_planes(m, n_slots, slot_ids, size, 0, self.device)
         if transition is not None or trimap:
-            from . import groundtruth
             if alphas_u8 is None:
                 raise ValueError('transition / trimap are made from the alphas: alphas_u8 is missing')
             a = alphas_u8.reshape(T, -1, H, W)
@@ -129,14 +124,7 @@ class DevicePreprocessor:
         crops -- the mask chain of `mask_draws` (made for the cropped size), `/ 255` into the slots, `transition`. 'image' comes from the crop's
         own Normalize epilogue: the uint8 crop of the frames is never stored. `lut`: a (3, 256) uint8 tone curve for the frames (utils/crop.py).
         Image training passes the alphas as `masks_u8` too (him.py:103); the same object is cropped once."""
-        from . import crop
-        if len(frames_u8.shape) != 4:
-            raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
-        image, a, m = crop.apply(frames_u8, alphas_u8, None if masks_u8 is alphas_u8 else masks_u8, crop_draws, normalize=True, lut=lut,
-                                 mean=self.mean, std=self.std, device=self.device)
-        if masks_u8 is alphas_u8:
-            m = a
-        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
+        return self._train_item(frames_u8, alphas_u8, masks_u8, crop_draws, None, None, slot_ids, transition, mask_draws, lut, False)
 
     def train_item_affine(self, frames_u8, alphas_u8, masks_u8, crop_draws, affine_draws, slot_ids=None, *, transition=None, mask_draws=None,
                           lut=None, warp_masks=False):
@@ -146,62 +134,56 @@ class DevicePreprocessor:
         channel shift and Normalize; 'alpha' and `transition` come from the warped alphas. The reference does not warp the masks: with
         `warp_masks=False` (the image loader, him.py:49-57) the mask chain reads the UNWARPED cropped masks, also when `masks_u8 is alphas_u8`;
         `warp_masks=True` (the video loader, which regenerates the masks from the alphas afterwards, vim.py:55-59) hands it the warped alphas."""
-        from . import affine, crop
-        if affine_draws is not None and not isinstance(affine_draws, affine.AffineDraws):
-            raise TypeError('affine_draws must be an affine.AffineDraws or None (got %s)' % type(affine_draws).__name__)
-        if affine_draws is None or not affine_draws.fired:
-            return self.train_item(frames_u8, alphas_u8, masks_u8, crop_draws, slot_ids, transition=transition, mask_draws=mask_draws, lut=lut)
-        if len(frames_u8.shape) != 4:
-            raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
-        f, a, m = crop.apply(frames_u8, alphas_u8, None if (masks_u8 is alphas_u8 or warp_masks) else masks_u8, crop_draws, normalize=False,
-                             lut=lut, device=self.device)
-        if masks_u8 is alphas_u8 and not warp_masks:
-            m = a
-        image, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
-        if warp_masks and masks_u8 is not None:
-            m = a
-        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
+        return self._train_item(frames_u8, alphas_u8, masks_u8, crop_draws, None, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks)
 
     def train_item_photo(self, frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws=None, slot_ids=None, *, transition=None,
                          mask_draws=None, lut=None, warp_masks=False):
         """`train_item` / `train_item_affine` with the photometric steps that follow the flip in the reference's stream (GammaContrast,
         AdditiveGaussionNoise, JpegCompression: him.py:46-48, vim.py:51-54; utils/photometric.py) between the crop and RandomAffine.
         `photo`: a photometric.PhotoDraws made for the cropped size, or None; `affine_draws`: as in `train_item_affine`, or None.
-        None, or draws with neither noise nor quality, give `train_item_affine` itself, bit for bit and through its code path; a `photo.lut`
-        then joins the crop's table, after `lut`, and the crop's own Normalize epilogue stays in use. Otherwise the raw uint8 crop (with `lut`)
+        None, or draws with neither noise nor quality, give `train_item_affine` itself, bit for bit and as a call of it; a `photo.lut` then
+        joins the crop's table, after `lut`, and the crop's own Normalize epilogue stays in use. Otherwise the raw uint8 crop (with `lut`)
         feeds `photometric.apply` (`photo.lut`, the noise, the JPEG round trip): with its Normalize epilogue when no affine fires, raw when
         one does, because the warp reads uint8. Alphas and masks are untouched, as in the reference (the alpha line of JpegCompression is
-        commented out). `train_item` and `train_item_affine` keep their signatures; this wiring is a method of its own, as the affine one is."""
-        from . import affine, crop, photometric
+        commented out). The three methods keep their signatures and share one wiring, `_train_item`."""
+        self._check_draws(photo, affine_draws)
+        if photo is None or not photo.fired:
+            if photo is not None and photo.lut is not None:
+                lut = photo.lut if lut is None else photometric.compose_luts(lut, photo.lut, resolve_device(self.device, frames_u8))
+            return self.train_item_affine(frames_u8, alphas_u8, masks_u8, crop_draws, affine_draws, slot_ids, transition=transition,
+                                          mask_draws=mask_draws, lut=lut, warp_masks=warp_masks)
+        return self._train_item(frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks)
+
+    @staticmethod
+    def _check_draws(photo, affine_draws):
         if photo is not None and not isinstance(photo, photometric.PhotoDraws):
             raise TypeError('photo must be a photometric.PhotoDraws or None (got %s)' % type(photo).__name__)
         if affine_draws is not None and not isinstance(affine_draws, affine.AffineDraws):
             raise TypeError('affine_draws must be an affine.AffineDraws or None (got %s)' % type(affine_draws).__name__)
-        if photo is None or not photo.fired:
-            if photo is not None and photo.lut is not None:
-                lut = photo.lut if lut is None else photometric.compose_luts(lut, photo.lut, self._device_of(frames_u8))
-            return self.train_item_affine(frames_u8, alphas_u8, masks_u8, crop_draws, affine_draws, slot_ids, transition=transition,
-                                          mask_draws=mask_draws, lut=lut, warp_masks=warp_masks)
+
+    def _train_item(self, frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks):
+        """The one wiring of the training item, in the order of the reference's stream: crop -> (noise / JPEG) -> (RandomAffine) -> assemble.
+        `photo`: fired PhotoDraws or None (a lone tone curve has joined `lut` by now). Every routing decision is made here, once; DESIGN.md
+        section 20 has the table of which launch writes 'image'."""
+        self._check_draws(photo, affine_draws)
         if len(frames_u8.shape) != 4:
             raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
         warped = affine_draws is not None and affine_draws.fired
-        f, a, m = crop.apply(frames_u8, alphas_u8, None if (masks_u8 is alphas_u8 or (warped and warp_masks)) else masks_u8, crop_draws,
-                             normalize=False, lut=lut, device=self.device)
-        if masks_u8 is alphas_u8 and not (warped and warp_masks):
+        # the mask chain reads the warped alphas (the video loader's wiring), or the cropped alphas when the masks ARE the alphas, or the
+        # cropped masks; only the last makes the crop touch `masks_u8`
+        shared, from_warp = masks_u8 is alphas_u8, warped and warp_masks and masks_u8 is not None
+        # Normalize belongs to the last stage that touches the frames: the crop's epilogue, the photometric one, or affine.shift_normalize
+        f, a, m = crop.apply(frames_u8, alphas_u8, None if (shared or from_warp) else masks_u8, crop_draws, normalize=photo is None and not warped,
+                             lut=lut, mean=self.mean, std=self.std, device=self.device)
+        if shared:
             m = a
-        if not warped:
-            image = photometric.apply(f, photo, normalize=True, mean=self.mean, std=self.std, device=self.device)
-        else:
-            f = photometric.apply(f, photo, normalize=False, device=self.device)
-            image, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
-            if warp_masks and masks_u8 is not None:
+        if photo is not None:
+            f = photometric.apply(f, photo, normalize=not warped, mean=self.mean, std=self.std, device=self.device)
+        if warped:                                                                                    # reads raw uint8
+            f, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
+            if from_warp:
                 m = a
-        return self._assemble(image, a, m, slot_ids, transition, False, mask_draws)
-
-    def _device_of(self, x):
-        if self.device is not None:
-            return torch.device(self.device)
-        return x.device if torch.is_tensor(x) and x.is_cuda else torch.device('cuda', torch.cuda.current_device())
+        return self._assemble(f, a, m, slot_ids, transition, False, mask_draws)
 
     def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):
         """The evaluation item of him.py:151-202 / vim.py:150-209 from decoded files: (T, h, w, 3) uint8 frames (a clip of T equal-sized
@@ -212,8 +194,7 @@ class DevicePreprocessor:
           'alpha'  `ori_alphas / 255` at the original size, no `< 5` rule (him.py:152);
           'trimap' from the original alphas (utils/groundtruth.py);
           'transform_info' the list `postprocessing.reverse_transform_tensor` reads."""
-        from . import geometry, groundtruth
-        frames = groundtruth._check_u8(frames_u8)
+        frames = check_u8(frames_u8)
         if frames.dim() == 3:
             frames = frames[None]
         if frames.dim() != 4 or frames.shape[-1] != 3:
@@ -229,7 +210,6 @@ class DevicePreprocessor:
         if m is not None:
             out['mask'] = geometry.resize_pad_planes(m, p, interpolation='nearest', down8=self.downscale_mask, device=self.device)
         else:
-            from . import maskgen
             g = maskgen.from_alpha(geometry.resize_pad_planes_u8(a, p, device=self.device), device=self.device)
             size = (p.out_h // 8, p.out_w // 8) if self.downscale_mask else None
             out['mask'] = scale_planes(g, None, None, size, 0, self.device)
@@ -242,8 +222,7 @@ class DevicePreprocessor:
     def predict_item(self, frame_u8, instance_masks_u8, *, short_size=576, divisor=64):
         """demo/maggie_predictor.py:34-50: one (h, w, 3) uint8 frame and its (n, h, w) uint8 instance masks (0 / 255) ->
         ({'image': (1, 1, 3, Hp, Wp), 'mask': (1, 1, n, Hp, Wp)}, transform_info); the masks keep the network's full size there."""
-        from . import geometry, groundtruth
-        frame = groundtruth._check_u8(frame_u8)
+        frame = check_u8(frame_u8)
         if frame.dim() != 3 or frame.shape[-1] != 3:
             raise ValueError('frame must be (h, w, 3) (got shape %s)' % (tuple(frame.shape),))
         h, w = (int(v) for v in frame.shape[:2])
@@ -256,8 +235,7 @@ class DevicePreprocessor:
     @staticmethod
     def _item_planes(x_u8, T, h, w, what):
         """uint8 (T, n, h, w) or (T * n, h, w) planes of an item, n >= 1 -> (T, n, h, w)."""
-        from . import groundtruth
-        x = groundtruth._check_u8(x_u8)
+        x = check_u8(x_u8)
         if x.dim() not in (3, 4) or tuple(x.shape[-2:]) != (h, w):
             raise ValueError('%s: expected (T, n, %d, %d) or (T * n, %d, %d) planes like the frames (got shape %s)' % (what, h, w, h, w, tuple(x.shape)))
         count = int(np.prod(x.shape[:-2]))

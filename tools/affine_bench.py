@@ -15,30 +15,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+from _timing import timed
 from maggie_amd.utils import affine
 
 dev = torch.device('cuda:0')
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 H = W = 512
-
-
-def timed(fns, reps=REPS):
-    """Median, minimum and quartiles (the run-to-run spread) of the device microseconds of every callable, alternated call by call after a
-    warm-up."""
-    for _ in range(10):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            ts[i].append(a.elapsed_time(b) * 1e3)
-    return [(float(np.median(t)), float(np.min(t)), float(np.percentile(t, 25)), float(np.percentile(t, 75))) for t in ts]
 
 
 def extreme_matrix():
@@ -82,7 +64,7 @@ def main():
         fns = [lambda: affine.apply(frames, alphas, d, regime='staged'), lambda: affine.apply(frames, alphas, d, regime='direct'), parent,
                lambda: affine.warp(frames[:0], alphas, d), lambda: affine.warp(frames, None, d, regime='staged'),
                lambda: affine.warp(frames, None, d, regime='direct'), lambda: affine.shift_normalize(warped, mm, d.shift)]
-        rows += list(zip(names, timed(fns)))
+        rows += list(zip(names, timed(fns, REPS)))
     print('%-100s %10s %10s %10s %10s' % ('workload (%d calls each)' % REPS, 'median us', 'min us', 'p25 us', 'p75 us'))
     for name, (med, mn, lo, hi) in rows:
         print('%-100s %10.1f %10.1f %10.1f %10.1f' % (name, med, mn, lo, hi))

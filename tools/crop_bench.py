@@ -15,31 +15,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+from _timing import timed
 from maggie_amd.utils import crop
 from maggie_amd.utils.preprocess import normalize_frames
 
 dev = torch.device('cuda:0')
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 H, W, CROP = 576, 768, (512, 512)
-
-
-def timed(fns, reps=REPS):
-    """Median, minimum and quartiles (the run-to-run spread) of the device microseconds of every callable, alternated call by call after a
-    warm-up."""
-    for _ in range(10):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            ts[i].append(a.elapsed_time(b) * 1e3)
-    return [(float(np.median(t)), float(np.min(t)), float(np.percentile(t, 25)), float(np.percentile(t, 75))) for t in ts]
 
 
 def main():
@@ -77,7 +59,7 @@ def main():
                  '  box of the alphas (mg_crop_bbox, no read-back)', '  three candidate windows (mg_crop_hits, no read-back)']
         fns = [fused(True), fused(False), parent, lambda: crop.apply(frames, alphas, masks, pd, normalize=True), lambda: crop.bbox(alphas),
                lambda: crop.window_hits(alphas, windows, CROP)]
-        rows += list(zip(names, timed(fns)))
+        rows += list(zip(names, timed(fns, REPS)))
     print('%-100s %10s %10s %10s %10s' % ('workload (%d calls each)' % REPS, 'median us', 'min us', 'p25 us', 'p75 us'))
     for name, (med, mn, lo, hi) in rows:
         print('%-100s %10.1f %10.1f %10.1f %10.1f' % (name, med, mn, lo, hi))

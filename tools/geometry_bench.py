@@ -26,6 +26,7 @@ STEP_LIMIT = 120               # seconds per timed step
 def one(size, step, reps):
     import numpy as np
     import torch
+    from _timing import timed
     from maggie_amd.utils import geometry as GE
     from maggie_amd.utils.preprocess import normalize_frames
     dev = torch.device('cuda:0')
@@ -55,18 +56,8 @@ def one(size, step, reps):
     else:
         padded = torch.from_numpy(rs.randint(0, 256, size=(1, p.out_h, p.out_w, 3)).astype(np.uint8)).to(dev)
         fn, moved = (lambda: normalize_frames(padded)), out_px * 15
-    for _ in range(10):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return {'median_us': float(np.median(ts)), 'min_us': float(np.min(ts)), 'bytes': float(moved), 'bound_us': moved / (HBM_COPY_TBS * 1e12) * 1e6,
+    median, fastest = timed([fn], reps)[0][:2]
+    return {'median_us': median, 'min_us': fastest, 'bytes': float(moved), 'bound_us': moved / (HBM_COPY_TBS * 1e12) * 1e6,
             'regime': 'shared' if p.tables['regime'] == GE.SHARED_ROWS else 'direct', 'out': [p.out_h, p.out_w]}
 
 

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 from scipy import ndimage
 
+from _timing import timed
 from maggie_amd.utils import groundtruth as G
 from oracle.region import ellipse_kernel
 
@@ -30,19 +31,8 @@ def soft(rs, H, W, cy=None, cx=None):
 
 
 def gpu_us(fn, reps=50):
-    """Median over `reps` launches, each bracketed by its own event pair, after a warm-up."""
-    for _ in range(5):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        torch.cuda.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3)
-    return float(np.median(ts)), float(np.min(ts))
+    """Median and minimum over `reps` launches, each bracketed by its own event pair, after a warm-up."""
+    return timed([fn], reps, warmup=5)[0][:2]
 
 
 def scipy_ms(planes, k, n, erode=True):

@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+from _timing import timed
 from maggie_amd.utils import groundtruth as G
 from maggie_amd.utils import maskgen as MG
 
@@ -26,24 +27,6 @@ def soft(rs, H, W):
     cy, cx = rs.uniform(0.2 * H, 0.8 * H), rs.uniform(0.2 * W, 0.8 * W)
     d = (1.0 - np.sqrt(((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2)) * min(ry, rx)
     return np.clip(np.rint((0.5 + d / 6.0) * 255), 0, 255).astype(np.uint8)
-
-
-def timed(fns, reps=REPS):
-    """Median and minimum device microseconds of every callable, alternated call by call after a warm-up."""
-    for _ in range(10):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            ts[i].append(a.elapsed_time(b) * 1e3)
-    return [(float(np.median(t)), float(np.min(t))) for t in ts]
 
 
 def main():
@@ -72,7 +55,7 @@ def main():
         fns = [lambda: MG.synthesize(planes, draws), lambda: MG.binarize_morph(planes, worst_dev), lambda: MG.binarize_morph(noise, worst_dev),
                lambda: MG.down_up(planes, ones), lambda: MG.cut(planes, cut), lambda: MG.stats(planes), lambda: MG.drop(planes, sel, st),
                lambda: G.dilate_erode(planes, kn), lambda: G.dilate_erode(noise, kn)]
-        rows += list(zip(names, timed(fns)))
+        rows += list(zip(names, [t[:2] for t in timed(fns, REPS)]))
         if kind == 'video':                                               # with the drop-out: a host synchronisation inside, so a host clock
             dd = MG.draw_chain(np.random.RandomState(1), random.Random(1), P, H, W, dropout=True, from_alpha=True).to(dev)
             dr = np.random.RandomState(2)

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+from _timing import timed
 from maggie_amd.utils import photometric
 from maggie_amd.utils.preprocess import normalize_frames
 
@@ -26,25 +27,6 @@ except ImportError:
 dev = torch.device('cuda:0')
 REPS = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 H, W, QUALITY = 512, 512, 35
-
-
-def timed(fns, reps=REPS):
-    """Median, minimum and quartiles (the run-to-run spread) of the microseconds between the event pair around every callable, alternated
-    call by call after a warm-up. The parent's host work lies between its events too."""
-    for _ in range(10):
-        for fn in fns:
-            fn()
-    torch.cuda.synchronize()
-    ts = [[] for _ in fns]
-    for _ in range(reps):
-        for i, fn in enumerate(fns):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            torch.cuda.synchronize()
-            ts[i].append(a.elapsed_time(b) * 1e3)
-    return [(float(np.median(t)), float(np.min(t)), float(np.percentile(t, 25)), float(np.percentile(t, 75))) for t in ts]
 
 
 def pillow(x):
@@ -97,7 +79,7 @@ def main():
             toned = np.stack([lut[c][host[..., c]] for c in range(3)], -1)
             noisy = np.clip(toned.astype(np.int32) + noise, 0, 255).astype(np.uint8)
             assert torch.equal(full(), normalize_frames(torch.from_numpy(pillow(noisy)).to(dev)))
-        rows += list(zip(names, timed(fns)))
+        rows += list(zip(names, timed(fns, REPS)))
     print('%-90s %10s %10s %10s %10s' % ('workload (%d calls each)' % REPS, 'median us', 'min us', 'p25 us', 'p75 us'))
     for name, (med, mn, lo, hi) in rows:
         print('%-90s %10.1f %10.1f %10.1f %10.1f' % (name, med, mn, lo, hi))

@@ -12,6 +12,7 @@
 // accumulators stay in registers across the rows of a group and are reduced wave -> LDS -> one atomicAdd per value per block.
 // All kernels are HBM/L2-bound: F is read once (forward) / twice (backward) per direction.
 #include "common.h"
+#include "launch.h"
 #include <stdlib.h>
 #include "../../include/maggie_hip.h"
 
@@ -509,7 +510,7 @@ __global__ __launch_bounds__(NT) void feat_bwd_kernel(const float* __restrict__ 
 
 inline dim3 row_grid(int L, int B) { return dim3((L + RPB - 1) / RPB, B); }
 inline int fwd_rows_per_group() {                               // MG_ATTN_FWD_RG = 1 | 2 | 4 (A/B switch)
-    static const int v = [] { const char* e = getenv("MG_ATTN_FWD_RG"); const int x = e ? atoi(e) : 1; return (x == 1 || x == 2) ? x : 4; }();
+    static const int v = [] { const int x = (int)mg_env_long("MG_ATTN_FWD_RG", 1); return (x == 1 || x == 2) ? x : 4; }();
     return v;
 }
 inline int attn_check(int B, int T, int L, int Dm, int NID) {

@@ -19,6 +19,7 @@
 // LDS image of a stage: halo [TH + 2][24 px][64 B] (slot = chunk ^ 2 * ((px >> 2) & 1)) | weights [9 taps][BN rows][64 B]
 // (slot = chunk ^ 3 * ((row >> 3) & 1)), both conflict-free for ds_read_b128 (as in conv_igemm.hip).
 #include "common.h"
+#include "launch.h"
 #include "conv_xcd.h"
 #include "conv_forms.h"
 #include "../../include/maggie_hip.h"
@@ -1080,15 +1081,9 @@ int launch_h3_slab(const mg_conv_params& p, hipStream_t st) {
     constexpr size_t lds = (size_t)2 * HC::A_BYTES + HC::B_BYTES;
     static_assert(3 * lds <= 160 * 1024, "three workgroups per CU");
     const bool res = p.res || p.res2;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
     const long tiles = (long)p.N * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16);
     if (mg_det_on && p.stats && p.stat_mode == 0 && (long)(p.stat_rep > 0 ? p.stat_rep : MG_STAT_REPLICAS) < tiles) return -8;
-    const long maxwg = 3l * ncu, per = (tiles + maxwg - 1) / maxwg;
+    const long maxwg = 3l * mg_cu_count(), per = (tiles + maxwg - 1) / maxwg;
     dim3 grid(xcd_grid((tiles + per - 1) / per));
 #define H3_SLAB(MODE_, RES_, XF_) do { MG_FORM(MG_FF_H3_SLAB, 0, 0, 0, 0, MODE_, (RES_ ? MG_FORM_RES : 0) | (XF_ ? MG_FORM_XF : 0)); \
         hipLaunchKernelGGL((conv_halo3_slab_kernel<T, MODE_, RES_, XF_>), grid, dim3(256), lds, st, p); } while (0)
@@ -1113,53 +1108,34 @@ int launch_h3(const mg_conv_params& p, hipStream_t st) {
     using HC = H3Cfg<TH, BN, NS>;
     constexpr size_t lds = HC::LDS;
     const bool res = p.res || p.res2;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const long mtiles = (long)p.N * ((p.Hout + TH - 1) / TH) * ((p.Wout + 15) / 16);
     const long tiles = mtiles * ((p.Cout + BN - 1) / BN);
     if (mg_det_on && p.stats && p.stat_mode == 0 && (long)(p.stat_rep > 0 ? p.stat_rep : MG_STAT_REPLICAS) < mtiles) return -8;
     dim3 grid(xcd_grid(tiles));
-    if (p.xf_scale) {                                        // BatchNorm + activation of the producing layer applied to the staged halo (forward only)
+    // (the flags after NS: MODE, RES, XF, BNB)
+#define H3_GO(LDS_, ...) MG_LAUNCH_LDS((conv_halo3_kernel<T, TH, BN, NS, __VA_ARGS__>), grid, dim3(NS > 1 ? 512 : 256), LDS_, st, p)
+    // (the plain forms first: the kernels leave the compiler in the order in which the launcher names them, and that order is kept as it was)
+    if (!p.xf_scale && !p.bnb_x) {
+        MG_FORM(MG_FF_H3, TH, BN, NS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, res ? MG_FORM_RES : 0);
+        if (p.mode == MG_MODE_CONV) {
+            if (!res) H3_GO(lds, MG_MODE_CONV, false);
+            else H3_GO(lds, MG_MODE_CONV, true);
+        } else {
+            if (!res) H3_GO(lds, MG_MODE_TCONV, false);
+            else H3_GO(lds, MG_MODE_TCONV, true);
+        }
+    } else if (p.xf_scale) {                                 // BatchNorm + activation of the producing layer applied to the staged halo (forward only)
         constexpr size_t lds_xf = lds + 4096;                    // + the [2 * Cin] fp32 table (Cin <= 512)
         if (p.mode != MG_MODE_CONV || p.Cin > 512 || lds_xf > 160 * 1024) return MG_XF_UNSUPPORTED;
-        static bool xf_attr = false;
-        if (!xf_attr) {
-            (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xf);
-            (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xf);
-            xf_attr = true;
-        }
         MG_FORM(MG_FF_H3, TH, BN, NS, 0, MG_MODE_CONV, MG_FORM_XF | (res ? MG_FORM_RES : 0));
-        if (res) hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true, true>), grid, dim3(NS > 1 ? 512 : 256), lds_xf, st, p);
-        else hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false, true>), grid, dim3(NS > 1 ? 512 : 256), lds_xf, st, p);
-        MG_CHECK_LAUNCH();
-        return 0;
-    }
-    if (p.bnb_x) {                                           // the data gradient of a 3x3 / stride 1 conv behind a training BatchNorm layer (BnLink)
+        if (!res) H3_GO(lds_xf, MG_MODE_CONV, false, true);
+        else H3_GO(lds_xf, MG_MODE_CONV, true, true);
+    } else {                                                 // the data gradient of a 3x3 / stride 1 conv behind a training BatchNorm layer (BnLink)
         if (p.mode != MG_MODE_TCONV || !p.stats || p.stat_mode != 0) return -2;
-        static bool bnb_attr = false;
-        if (!bnb_attr) {
-            (void)hipFuncSetAttribute((const void*)conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            bnb_attr = true;
-        }
         MG_FORM(MG_FF_H3, TH, BN, NS, 0, MG_MODE_TCONV, MG_FORM_RES | MG_FORM_BNB);
-        hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true, false, true>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
-        MG_CHECK_LAUNCH();
-        return 0;
+        H3_GO(lds, MG_MODE_TCONV, true, false, true);
     }
-    MG_FORM(MG_FF_H3, TH, BN, NS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, res ? MG_FORM_RES : 0);
-    if (p.mode == MG_MODE_CONV) {
-        if (res) hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, true>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
-        else hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_CONV, false>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
-    } else {
-        if (res) hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, true>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
-        else hipLaunchKernelGGL((conv_halo3_kernel<T, TH, BN, NS, MG_MODE_TCONV, false>), grid, dim3(NS > 1 ? 512 : 256), lds, st, p);
-    }
+#undef H3_GO
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -1170,31 +1146,22 @@ int launch_h3_persist(const mg_conv_params& p, hipStream_t st) {
     constexpr size_t lds = (size_t)NS * HC::STAGE + HC::STAT_BYTES;
     static_assert(lds <= 160 * 1024, "LDS of the persistent form");
     const bool res = p.res || p.res2;
-    static bool attr_set = false;
-    static int ncu = 256;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_TCONV, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute((const void*)conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_TCONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-        attr_set = true;
-    }
     const long mtiles = (long)p.N * ((p.Hout + TH - 1) / TH) * ((p.Wout + 15) / 16);
     const long tiles = mtiles * ((p.Cout + BN - 1) / BN);
     if (mg_det_on && p.stats && p.stat_mode == 0 && (long)(p.stat_rep > 0 ? p.stat_rep : MG_STAT_REPLICAS) < mtiles) return -8;
+    const int ncu = mg_cu_count();
     long g = tiles < ncu ? tiles : ncu;
     dim3 grid(xcd_grid(g));
     MG_FORM(MG_FF_H3_PERSIST, TH, BN, NS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, res ? MG_FORM_RES : 0);
+#define H3P_GO(MODE_, RES_) MG_LAUNCH_LDS((conv_halo3_persist_kernel<T, TH, BN, NS, MODE_, RES_>), grid, dim3(512), lds, st, p)
     if (p.mode == MG_MODE_CONV) {
-        if (res) hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, true>), grid, dim3(512), lds, st, p);
-        else hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_CONV, false>), grid, dim3(512), lds, st, p);
+        if (!res) H3P_GO(MG_MODE_CONV, false);
+        else H3P_GO(MG_MODE_CONV, true);
     } else {
-        if (res) hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_TCONV, true>), grid, dim3(512), lds, st, p);
-        else hipLaunchKernelGGL((conv_halo3_persist_kernel<T, TH, BN, NS, MG_MODE_TCONV, false>), grid, dim3(512), lds, st, p);
+        if (!res) H3P_GO(MG_MODE_TCONV, false);
+        else H3P_GO(MG_MODE_TCONV, true);
     }
+#undef H3P_GO
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -1219,7 +1186,7 @@ int dispatch_h3(const mg_conv_params& p, hipStream_t st) {
         else { ns = 4; if (t32 < 200 || p.Hout < 8) th = 4; }
         if (p.Hout < 8) th = 4;
         if (th == 4 && !(bn == 32 && ns == 4)) { bn = 32; ns = 4; }
-        static const int xf_single = [] { const char* e = getenv("MG_H3_XF_SINGLE"); return e ? atoi(e) : 1; }();   // A/B: 0 = operand transform of Cin > 64 layers in the ring form only
+        static const int xf_single = (int)mg_env_long("MG_H3_XF_SINGLE", 1);   // A/B: 0 = operand transform of Cin > 64 layers in the ring form only
         if (!xf_single && p.xf_scale && ns == 1 && p.Cin > 64) ns = bn == 64 ? 3 : 4;
     }
     // one slab, one channel tile, >= ~5 tiles per resident workgroup: the persistent form with the weights staged once (ns 201 forces it, 200 forbids it).
@@ -1227,7 +1194,7 @@ int dispatch_h3(const mg_conv_params& p, hipStream_t st) {
     // C32 -> 8 data gradient 34.3 (round-2 im2col form) | 29.7; batch 12 512 x 512 131.5 | 115.7, 256 x 256 30.7 | 26.5; batch 4 256 x 256 (2 048 tiles,
     // 2.7 per workgroup) 13.0 | 14.3 -- hence the threshold. PMC (profiles/r06_pmc_slab.txt, C32 512 x 512 forward, per launch): vector-ALU instructions
     // 13.6 M -> 6.4 M (414 -> 194 per wave and tile), L2 read requests 1.59 M -> 0.82 M, wave cycles 57.9 M -> 35.3 M; the matrix pipe's share is 11 us of the 42.
-    static const int slab_min = [] { const char* e = getenv("MG_H3_SLAB_MIN"); return e ? atoi(e) : 4096; }();
+    static const int slab_min = (int)mg_env_long("MG_H3_SLAB_MIN", 4096);
     if (ns != 200 && nstage == 1 && p.Cout <= 32 && !p.bnb_x && (ns == 201 || (!g_h3_force[0] && sp8 >= slab_min))) return launch_h3_slab<T>(p, st);
     if (ns >= 200 || p.Cout < 16) return 1;
     if (ns >= 100) {                                         // persistent ring forms (forced: mg_set_halo3_cfg(TH, BN, 100 + NS); chosen: see above)
@@ -1247,9 +1214,8 @@ void h3_init() {
     static bool done = false;
     if (done) return;
     done = true;
-    const char* e = getenv("MG_HALO3");
-    if (g_h3_enabled < 0) g_h3_enabled = e ? atoi(e) : 1;
-    if (const char* f = getenv("MG_H3_CFG")) sscanf(f, "%d,%d,%d", &g_h3_force[0], &g_h3_force[1], &g_h3_force[2]);
+    if (g_h3_enabled < 0) g_h3_enabled = (int)mg_env_long("MG_HALO3", 1);
+    if (const char* f = mg_env_str("MG_H3_CFG")) sscanf(f, "%d,%d,%d", &g_h3_force[0], &g_h3_force[1], &g_h3_force[2]);
 }
 
 bool h3_eligible(const mg_conv_params& p) {

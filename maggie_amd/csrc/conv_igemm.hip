@@ -16,6 +16,7 @@
 // Epilogue goes through an fp32 LDS tile so global stores / residual loads are 16-byte vectors and the per-channel
 // BatchNorm statistics (sum, sum of squares) are reduced per block before one atomicAdd per channel.
 #include "common.h"
+#include "launch.h"
 #include "conv_xcd.h"
 #include "conv_forms.h"
 #include "../../include/maggie_hip.h"
@@ -1189,10 +1190,10 @@ static inline int stat_rows_check(const mg_conv_params& p, long mtiles) {
 }
 
 static inline bool halo_eligible(const mg_conv_params& p) {
-    static const int enabled = [] { const char* e = getenv("MG_FPROP_HALO"); return e ? atoi(e) : 1; }();
+    static const int enabled = (int)mg_env_long("MG_FPROP_HALO", 1);
     if (!enabled || !MG_IS16(p.dtype) || p.m_dev || p.mode == MG_MODE_GATHER) return false;
     // Cin >= 96: three-stage ring over the 32-channel slabs; Cin 32 / 64: single-stage form (halo_small)
-    static const int small = [] { const char* e = getenv("MG_FPROP_HALO_SMALL"); return e ? atoi(e) : 1; }();
+    static const int small = (int)mg_env_long("MG_FPROP_HALO_SMALL", 1);
     if (p.R != 3 || p.S != 3 || p.stride != 1 || p.dil != 1 || p.pad != 1 || p.Cin % 32 != 0) return false;
     if (p.Cin < 96 ? (!small || p.Cout < 8 || p.Cout % 8 != 0) : p.Cout < 64) return false;
     if (p.Hin != p.Hout || p.Win != p.Wout || p.Wout < 16 || p.Hout < 4) return false;
@@ -1202,50 +1203,42 @@ static inline bool halo_eligible(const mg_conv_params& p) {
 template <typename T, int TH, int BN = 64, int NS = 3>
 static int launch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
     constexpr size_t lds = HaloCfg<TH, BN, NS>::LDS;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, true, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const long tiles = (long)p.N * ((p.Hout + TH - 1) / TH) * ((p.Wout + 15) / 16) * ((p.Cout + BN - 1) / BN);
     if (int rcs = stat_rows_check(p, (long)p.N * ((p.Hout + TH - 1) / TH) * ((p.Wout + 15) / 16))) return rcs;
     dim3 grid(xcd_grid(tiles));
-    if (p.xf_scale) {                                        // BatchNorm + activation of the producing layer applied to the staged halo (forward only)
-        if constexpr (NS <= 2 && BN >= 32) {
-            constexpr size_t lds_xf = lds + 4096;            // + the [2 * Cin] fp32 table (Cin <= 512)
-            if (p.mode != MG_MODE_CONV || p.bnb_x || p.Cin > 512 || lds_xf > 160 * 1024) return MG_XF_UNSUPPORTED;
-            static bool xf_attr = false;
-            if (!xf_attr) {
-                hipFuncSetAttribute((const void*)igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_xf);
-                xf_attr = true;
+    // (the plain forms first: the kernels leave the compiler in the order in which the launcher names them, and that order is kept as it was)
+    if (!p.xf_scale) {
+        if (!p.bnb_x) {
+            if (p.mode == MG_MODE_CONV) {
+                MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, 0);
+                MG_LAUNCH_LDS((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p);
+            } else {
+                MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, 0);
+                MG_LAUNCH_LDS((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p);
             }
-            MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, MG_FORM_XF);
-            hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T, true>), grid, dim3(256), lds_xf, st, p);
-            MG_CHECK_LAUNCH();
-            return 0;
-        } else return MG_XF_UNSUPPORTED;
+        } else {                                             // the data gradient of a 3x3 / stride 1 conv behind a BatchNorm layer
+            if (p.mode != MG_MODE_TCONV) return -2;
+            MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, MG_FORM_BNB);
+            MG_LAUNCH_LDS((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, true, T>), grid, dim3(256), lds, st, p);
+        }
+        MG_CHECK_LAUNCH();
+        return 0;
     }
-    if (p.bnb_x) {                                           // the data gradient of a 3x3 / stride 1 conv behind a BatchNorm layer
-        if (p.mode != MG_MODE_TCONV) return -2;
-        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, MG_FORM_BNB);
-        hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, true, T>), grid, dim3(256), lds, st, p);
-    } else if (p.mode == MG_MODE_CONV) {
-        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, 0);
-        hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p);
-    } else {
-        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_TCONV, 0);
-        hipLaunchKernelGGL((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p);
-    }
-    MG_CHECK_LAUNCH();
-    return 0;
+    // BatchNorm + activation of the producing layer applied to the staged halo (forward only)
+    if constexpr (NS <= 2 && BN >= 32) {
+        constexpr size_t lds_xf = lds + 4096;                // + the [2 * Cin] fp32 table (Cin <= 512)
+        if (p.mode != MG_MODE_CONV || p.bnb_x || p.Cin > 512 || lds_xf > 160 * 1024) return MG_XF_UNSUPPORTED;
+        MG_FORM(MG_FF_HALO, TH, BN, NS, 0, MG_MODE_CONV, MG_FORM_XF);
+        MG_LAUNCH_LDS((igemm_fprop_halo_kernel<TH, BN, NS, MG_MODE_CONV, false, T, true>), grid, dim3(256), lds_xf, st, p);
+        MG_CHECK_LAUNCH();
+        return 0;
+    } else return MG_XF_UNSUPPORTED;
 }
 
 template <typename T>
 static int dispatch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
     // 8 x 16 pixel tiles when they still give about one workgroup per CU (a workgroup holds a whole CU's LDS), else 4 x 16
-    static const long want = [] { const char* e = getenv("MG_HALO_BLOCKS"); return e ? atol(e) : 200l; }();
+    static const long want = mg_env_long("MG_HALO_BLOCKS", 200l);
     if (p.Cin < 96) {
         if (p.Cout <= 16) return p.Hout >= 8 ? launch_fprop_halo<T, 8, 16, 1>(p, st) : launch_fprop_halo<T, 4, 16, 1>(p, st);   // the 8-channel network input's data gradient
         if (p.Cout <= 32) return p.Hout >= 8 ? launch_fprop_halo<T, 8, 32, 1>(p, st) : launch_fprop_halo<T, 4, 32, 1>(p, st);
@@ -1255,7 +1248,7 @@ static int dispatch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
     // 32-channel-wide tiles with a two-slab ring: 66 KiB of LDS -> TWO workgroups per CU, whose load / MFMA / epilogue phases overlap (the
     // 64-wide three-slab form owns the whole CU). Costs 30 % more halo traffic; measured C512->256 32x32 18.0 -> 15.5 us, C256->128 64x64
     // 15.2 -> 14.1 us, C128 / C256 unchanged, step 14.91 -> 14.74 ms. MG_HALO_NARROW=0 selects the wide form.
-    static const int narrow = [] { const char* e = getenv("MG_HALO_NARROW"); return e ? atoi(e) : 1; }();
+    static const int narrow = (int)mg_env_long("MG_HALO_NARROW", 1);
     if (p.xf_scale && p.Hout >= 8) return launch_fprop_halo<T, 8, 32, 2>(p, st);      // the operand transform lives in the one- / two-slab forms
     if (narrow && p.Hout >= 8) return launch_fprop_halo<T, 8, 32, 2>(p, st);      // (4 x 16 tiles for the layers with < 300 workgroups: no gain, measured)
     if (t8 >= want && p.Hout >= 8) return launch_fprop_halo<T, 8>(p, st);
@@ -1265,7 +1258,7 @@ static int dispatch_fprop_halo(const mg_conv_params& p, hipStream_t st) {
 static inline bool async_eligible(const mg_conv_params& p) {
     // 1 (default): the 1x1 layers and the sparse gather convs (measured: 1x1 C128->64 15.6 -> 10.5 us; neutral or slightly slower than the
     // register-staged loop on the dense 3x3 shapes that the halo kernel does not take); 2: every aligned layer; 0: off
-    static const int enabled = [] { const char* e = getenv("MG_FPROP_ASYNC"); return e ? atoi(e) : 1; }();
+    static const int enabled = (int)mg_env_long("MG_FPROP_ASYNC", 1);
     if (!enabled || !MG_IS16(p.dtype) || p.Cin % 32 != 0 || p.Cout <= 32) return false;
     if (enabled == 1 && !(p.R * p.S == 1 || p.mode == MG_MODE_GATHER)) return false;
     if (p.mode == MG_MODE_TCONV && !(p.stride == 1 || p.stride == 2 || p.stride == 4)) return false;
@@ -1276,42 +1269,29 @@ static inline bool async_eligible(const mg_conv_params& p) {
 template <typename T, int BM, int BN, int KS, int NS>
 int launch_fprop_async(const mg_conv_params& p, hipStream_t st) {
     constexpr size_t lds = async_lds_bytes<BM, BN, KS, NS>();
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_CONV, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_GATHER, false, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_CONV, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_GATHER, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, true, T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     const long tiles = (long)((p.M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
     if (int rcs = stat_rows_check(p, (p.M + BM - 1) / BM)) return rcs;
-    if (p.bnb_x) {                                           // data gradient of a 1x1 conv behind a BatchNorm layer
-        if (p.m_dev || p.mode != MG_MODE_TCONV) return -2;
-        MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, MG_MODE_TCONV, MG_FORM_BNB);
-        hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, true, T>), dim3(xcd_grid(tiles)), dim3(256), lds, st, p);
-        MG_CHECK_LAUNCH();
-        return 0;
-    }
-    if (p.m_dev) {
+    // (the plain forms first: the kernels leave the compiler in the order in which the launcher names them, and that order is kept as it was)
+    if (!p.bnb_x && !p.m_dev) {
+        dim3 grid(xcd_grid(tiles));
+        if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, p.mode, 0);
+        switch (p.mode) {
+            case MG_MODE_CONV: MG_LAUNCH_LDS((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p); break;
+            case MG_MODE_TCONV: MG_LAUNCH_LDS((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p); break;
+            case MG_MODE_GATHER: MG_LAUNCH_LDS((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_GATHER, false, T>), grid, dim3(256), lds, st, p); break;
+            default: return -2;
+        }
+    } else if (!p.bnb_x) {
         const long g = tiles < 2048 ? tiles : 2048;
         dim3 pg(xcd_grid(g < 1 ? 1 : g));
         if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_GATHER) MG_FORM(MG_FF_ASYNC_MDEV, BM, BN, KS, NS, p.mode, 0);
-        if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_CONV, T>), pg, dim3(256), lds, st, p);
-        else if (p.mode == MG_MODE_GATHER) hipLaunchKernelGGL((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_GATHER, T>), pg, dim3(256), lds, st, p);
+        if (p.mode == MG_MODE_CONV) MG_LAUNCH_LDS((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_CONV, T>), pg, dim3(256), lds, st, p);
+        else if (p.mode == MG_MODE_GATHER) MG_LAUNCH_LDS((igemm_fprop_async_persistent_kernel<BM, BN, KS, NS, MG_MODE_GATHER, T>), pg, dim3(256), lds, st, p);
         else return -2;
-        MG_CHECK_LAUNCH();
-        return 0;
-    }
-    dim3 grid(xcd_grid(tiles));
-    if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, p.mode, 0);
-    switch (p.mode) {
-        case MG_MODE_CONV: hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_CONV, false, T>), grid, dim3(256), lds, st, p); break;
-        case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, false, T>), grid, dim3(256), lds, st, p); break;
-        case MG_MODE_GATHER: hipLaunchKernelGGL((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_GATHER, false, T>), grid, dim3(256), lds, st, p); break;
-        default: return -2;
+    } else {                                                 // data gradient of a 1x1 conv behind a BatchNorm layer
+        if (p.m_dev || p.mode != MG_MODE_TCONV) return -2;
+        MG_FORM(MG_FF_ASYNC, BM, BN, KS, NS, MG_MODE_TCONV, MG_FORM_BNB);
+        MG_LAUNCH_LDS((igemm_fprop_async_kernel<BM, BN, KS, NS, MG_MODE_TCONV, true, T>), dim3(xcd_grid(tiles)), dim3(256), lds, st, p);
     }
     MG_CHECK_LAUNCH();
     return 0;
@@ -1320,9 +1300,9 @@ int launch_fprop_async(const mg_conv_params& p, hipStream_t st) {
 // tile choice as in dispatch_fprop_ks (largest tile that still fills the chip); ring depth / stage width by K and tile
 template <typename T>
 static int dispatch_fprop_async(const mg_conv_params& p, hipStream_t st) {
-    static const long want = [] { const char* e = getenv("MG_FPROP_BLOCKS"); return e ? atol(e) : 768l; }();
+    static const long want = mg_env_long("MG_FPROP_BLOCKS", 768l);
     auto blocks = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn); };
-    static const int ns_small = [] { const char* e = getenv("MG_ASYNC_NS"); return e ? atoi(e) : 4; }();
+    static const int ns_small = (int)mg_env_long("MG_ASYNC_NS", 4);
     if (p.Cout > 64) {
         if (blocks(128, 128) >= want) return launch_fprop_async<T, 128, 128, 2, 3>(p, st);
         if (blocks(128, 64) >= want) return ns_small >= 4 ? launch_fprop_async<T, 128, 64, 2, 4>(p, st) : launch_fprop_async<T, 128, 64, 2, 3>(p, st);
@@ -1344,71 +1324,58 @@ int launch_fprop(const mg_conv_params& p, hipStream_t st) {
     dim3 grid(xcd_grid(row_tiles(p, p.M, BM) * ((p.Cout + BN - 1) / BN)));
     if (int rcs = stat_rows_check(p, row_tiles(p, p.M, BM))) return rcs;
     constexpr size_t lds = lds_bytes<BM, BN, KS>();
-    static bool attr_set = false;
-    if (lds > 65536 && !attr_set) {
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
+    // (the plain forms first: the kernels leave the compiler in the order in which the launcher names them, and that order is kept as it was)
+    if (!p.bnb_x && !p.m_dev) {
+        if (p.xf_scale) return MG_XF_UNSUPPORTED;
+        if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_FPROP, BM, BN, KS, 0, p.mode, tconv_phased(p) ? MG_FORM_PHASED : 0);
+        switch (p.mode) {
+            case MG_MODE_CONV: MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
+            case MG_MODE_TCONV: MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
+            case MG_MODE_GATHER: MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_GATHER>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
+            default: return -2;
+        }
+        MG_CHECK_LAUNCH();
+        return 0;
     }
     if (p.bnb_x) {                                           // a data-gradient launch that also accumulates a BatchNorm layer's backward sums
         if (p.m_dev) return -2;
         if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_TCONV) MG_FORM(MG_FF_FPROP, BM, BN, KS, 0, p.mode, MG_FORM_BNB | (tconv_phased(p) ? MG_FORM_PHASED : 0));
-        if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
-        else if (p.mode == MG_MODE_TCONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
+        if (p.mode == MG_MODE_CONV) MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
+        else if (p.mode == MG_MODE_TCONV) MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, false, true>), grid, dim3(256), lds, st, p, (float*)nullptr, 1);
         else return -2;
         MG_CHECK_LAUNCH();
         return 0;
     }
-    if (p.m_dev) {
-        // fixed persistent grid: enough workgroups to fill the chip (8 per CU at most), never more than the capacity needs
-        long cap_tiles = (long)((p.M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
-        long g = cap_tiles < 2048 ? cap_tiles : 2048;
-        dim3 pg(xcd_grid(g < 1 ? 1 : g));
-        static bool attr_set_p = false;
-        if (lds > 65536 && !attr_set_p) {
-            hipFuncSetAttribute((const void*)igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipFuncSetAttribute((const void*)igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set_p = true;
-        }
-        if (p.xf_scale) {                                    // sparse head: BatchNorm1d + activation of the producing layer applied on the operand's way into LDS
-            if constexpr (sizeof(T) == 2 && BM == 128 && BN <= 32 && KS <= 2) {
-                if (!fprop_xf_rows_ok(p)) return MG_XF_UNSUPPORTED;
-                MG_FORM(MG_FF_FPROP_MDEV, BM, BN, KS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_GATHER, MG_FORM_XF);
-                if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), pg, dim3(256), lds, st, p);
-                else hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER, true>), pg, dim3(256), lds, st, p);
-                MG_CHECK_LAUNCH();
-                return 0;
-            } else return MG_XF_UNSUPPORTED;
-        }
+    // device row count: a fixed persistent grid, enough workgroups to fill the chip (8 per CU at most), never more than the capacity needs
+    long cap_tiles = (long)((p.M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN);
+    long g = cap_tiles < 2048 ? cap_tiles : 2048;
+    dim3 pg(xcd_grid(g < 1 ? 1 : g));
+    if (!p.xf_scale) {
         if (p.mode == MG_MODE_CONV || p.mode == MG_MODE_GATHER) MG_FORM(MG_FF_FPROP_MDEV, BM, BN, KS, 0, p.mode, 0);
-        if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV>), pg, dim3(256), lds, st, p);
-        else if (p.mode == MG_MODE_GATHER) hipLaunchKernelGGL((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER>), pg, dim3(256), lds, st, p);
+        if (p.mode == MG_MODE_CONV) MG_LAUNCH_LDS((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV>), pg, dim3(256), lds, st, p);
+        else if (p.mode == MG_MODE_GATHER) MG_LAUNCH_LDS((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER>), pg, dim3(256), lds, st, p);
         else return -2;
         MG_CHECK_LAUNCH();
         return 0;
     }
-    if (p.xf_scale) return MG_XF_UNSUPPORTED;
-    if (p.mode >= MG_MODE_CONV && p.mode <= MG_MODE_GATHER) MG_FORM(MG_FF_FPROP, BM, BN, KS, 0, p.mode, tconv_phased(p) ? MG_FORM_PHASED : 0);
-    switch (p.mode) {
-        case MG_MODE_CONV: hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
-        case MG_MODE_TCONV: hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
-        case MG_MODE_GATHER: hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_GATHER>), grid, dim3(256), lds, st, p, (float*)nullptr, 1); break;
-        default: return -2;
-    }
-    MG_CHECK_LAUNCH();
-    return 0;
+    // sparse head: BatchNorm1d + activation of the producing layer applied on the operand's way into LDS
+    if constexpr (sizeof(T) == 2 && BM == 128 && BN <= 32 && KS <= 2) {
+        if (!fprop_xf_rows_ok(p)) return MG_XF_UNSUPPORTED;
+        MG_FORM(MG_FF_FPROP_MDEV, BM, BN, KS, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_GATHER, MG_FORM_XF);
+        if (p.mode == MG_MODE_CONV) MG_LAUNCH_LDS((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), pg, dim3(256), lds, st, p);
+        else MG_LAUNCH_LDS((igemm_fprop_persistent_kernel<T, BM, BN, KS, MG_MODE_GATHER, true>), pg, dim3(256), lds, st, p);
+        MG_CHECK_LAUNCH();
+        return 0;
+    } else return MG_XF_UNSUPPORTED;
 }
 
 template <typename T, int KS>
 int dispatch_fprop_ks(const mg_conv_params& p, hipStream_t st) {
     // Largest tile that still yields >= `want` blocks: these GEMMs are small, so exposed load latency is hidden by having
     // several co-resident blocks per CU (256 CUs), not by a deeper per-block pipeline.
-    static const long want = [] { const char* e = getenv("MG_FPROP_BLOCKS"); return e ? atol(e) : 768l; }();
+    static const long want = mg_env_long("MG_FPROP_BLOCKS", 768l);
     auto blocks = [&](int bm, int bn) { return row_tiles(p, p.M, bm) * ((p.Cout + bn - 1) / bn); };
-    static const long want_small = [] { const char* e = getenv("MG_FPROP_BLOCKS_SMALL"); return e ? atol(e) : 300l; }();   // below this many 64x64 blocks, 64x32 tiles (C512 16x16: +11 %, C256 32x32: +4 %)
+    static const long want_small = mg_env_long("MG_FPROP_BLOCKS_SMALL", 300l);   // below this many 64x64 blocks, 64x32 tiles (C512 16x16: +11 %, C256 32x32: +4 %)
     if (p.Cout > 64) {
         if (blocks(128, 128) >= want) return launch_fprop<T, 128, 128, KS>(p, st);
         if (blocks(128, 64) >= want) return launch_fprop<T, 128, 64, KS>(p, st);
@@ -1555,8 +1522,8 @@ struct SplitPlan { int bn, splits; };
 template <typename T>
 static SplitPlan plan_splitk(const mg_conv_params& p) {
     SplitPlan sp{0, 1};
-    static const int enabled = [] { const char* e = getenv("MG_FPROP_SPLITK"); return e ? atoi(e) : 1; }();
-    static const long want_small = [] { const char* e = getenv("MG_FPROP_BLOCKS_SMALL"); return e ? atol(e) : 300l; }();
+    static const int enabled = (int)mg_env_long("MG_FPROP_SPLITK", 1);
+    static const long want_small = mg_env_long("MG_FPROP_BLOCKS_SMALL", 300l);
     if (!enabled || p.mode == MG_MODE_GATHER || p.Cout < 64 || p.M > 8192 || p.m_dev) return sp;
     if (tconv_phased(p)) return sp;              // a quarter of the taps per phase: the K walk is short again
     if (halo_eligible(p)) return sp;             // the halo-tile kernel beats split-K on the deep 3x3 layers (C256 32x32: 30 -> 14 us)
@@ -1564,15 +1531,15 @@ static SplitPlan plan_splitk(const mg_conv_params& p) {
     const int nslab = (p.R * p.S * p.Cin + EPS - 1) / EPS;
     const int nstage = (nslab + 3) / 4;
     auto blocks = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.Cout + bn - 1) / bn); };
-    static const int min_stages = [] { const char* e = getenv("MG_SPLITK_MIN_K_STAGES"); return e ? atoi(e) : 18; }();   // K >= 2304 (bf16). Stand-alone launches: 48 -> 30 us
+    static const int min_stages = (int)mg_env_long("MG_SPLITK_MIN_K_STAGES", 18);   // K >= 2304 (bf16). Stand-alone launches: 48 -> 30 us
     // at 16x16x512 (K 4608), 53 -> 34 us at 32x32 512->256, even at K = 2304, a loss at K = 1152; inside the captured graphs (no host
     // cost for the extra launch) the forward + backward graphs take 13.60 / 13.43 / 13.25 / 13.40 ms for off / 24 / 18 / 9 stages
     if (nstage < min_stages || blocks(64, 64) >= want_small) return sp;
     sp.bn = p.Cout >= 128 ? 128 : 64;
     const long tiles = blocks(128, sp.bn);
-    static const long target = [] { const char* e = getenv("MG_SPLITK_BLOCKS"); return e ? atol(e) : 512l; }();
-    static const long smax = [] { const char* e = getenv("MG_SPLITK_MAX"); return e ? atol(e) : 8l; }();
-    static const long smin_stages = [] { const char* e = getenv("MG_SPLITK_MIN_STAGES"); return e ? atol(e) : 3l; }();
+    static const long target = mg_env_long("MG_SPLITK_BLOCKS", 512l);
+    static const long smax = mg_env_long("MG_SPLITK_MAX", 8l);
+    static const long smin_stages = mg_env_long("MG_SPLITK_MIN_STAGES", 3l);
     long s = (target + tiles - 1) / tiles;
     if (s > nstage / smin_stages) s = nstage / smin_stages;
     if (s > smax) s = smax;
@@ -1586,15 +1553,9 @@ static int launch_fprop_split(const mg_conv_params& p, float* ws, int splits, hi
     constexpr int BM = 128, KS = 4;
     dim3 grid(xcd_grid((long)((p.M + BM - 1) / BM) * ((p.Cout + BN - 1) / BN) * splits));
     constexpr size_t lds = lds_bytes<BM, BN, KS>();
-    static bool attr_set = false;
-    if (lds > 65536 && !attr_set) {
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipFuncSetAttribute((const void*)igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
     MG_FORM(MG_FF_SPLIT, BN, 0, 0, 0, p.mode == MG_MODE_CONV ? MG_MODE_CONV : MG_MODE_TCONV, 0);
-    if (p.mode == MG_MODE_CONV) hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), grid, dim3(256), lds, st, p, ws, splits);
-    else hipLaunchKernelGGL((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, true>), grid, dim3(256), lds, st, p, ws, splits);
+    if (p.mode == MG_MODE_CONV) MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_CONV, true>), grid, dim3(256), lds, st, p, ws, splits);
+    else MG_LAUNCH_LDS((igemm_fprop_kernel<T, BM, BN, KS, MG_MODE_TCONV, true>), grid, dim3(256), lds, st, p, ws, splits);
     MG_CHECK_LAUNCH();
     constexpr int CE = ElemTraits<T>::CE;
     const int cpr = (p.Cout + CE - 1) / CE, tx = cpr < 32 ? cpr : 32, ty = 256 / tx;
@@ -1681,13 +1642,13 @@ __global__ __launch_bounds__(256) void igemm_fprop_c8_kernel(const mg_conv_param
 }
 
 static inline bool fprop_c8_eligible(const mg_conv_params& p) {
-    static const int on = [] { const char* e = getenv("MG_FPROP_C8"); return e ? atoi(e) : 1; }();
+    static const int on = (int)mg_env_long("MG_FPROP_C8", 1);
     return on && MG_IS16(p.dtype) && p.mode == MG_MODE_CONV && !p.m_dev && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.dil == 1 &&
            p.Hout == p.Hin && p.Wout == p.Win && p.Cin == 8 && p.Cout <= 32 && p.ldx % 8 == 0;
 }
 template <typename T>
 static int launch_fprop_c8(const mg_conv_params& p, hipStream_t st) {
-    static const int th = [] { const char* e = getenv("MG_FPROP_C8_TH"); return e ? atoi(e) : 8; }();
+    static const int th = (int)mg_env_long("MG_FPROP_C8_TH", 8);
     if (int rcs = stat_rows_check(p, (long)p.N * ((p.Hout + 7) / 8) * ((p.Wout + 15) / 16))) return rcs;
     if (th == 16) {
         const long tiles = (long)p.N * ((p.Hout + 15) / 16) * ((p.Wout + 15) / 16);
@@ -1739,7 +1700,7 @@ int dispatch_fprop(const mg_conv_params& p, hipStream_t st) {
     const int nslab = (p.R * p.S * p.Cin + eps - 1) / eps;
     // stage width: 4 slabs (256 B of K per row) for the K-heavy layers, 2 slabs for K <= 576 (C32 / C64 3x3 layers: half the LDS
     // and staging registers -> more co-resident blocks; measured +31 % on the 512x512 C32 layers, +8 % on C64), 1 for tiny K
-    static const int ks2_max = [] { const char* e = getenv("MG_FPROP_KS2_MAX"); return e ? atoi(e) : 18; }();
+    static const int ks2_max = (int)mg_env_long("MG_FPROP_KS2_MAX", 18);
     if (nslab >= 8 && nslab <= ks2_max) return dispatch_fprop_ks<T, 2>(p, st);
     if (nslab >= 8) return dispatch_fprop_ks<T, 4>(p, st);
     return dispatch_fprop_ks<T, 1>(p, st);

@@ -1,6 +1,7 @@
 // Weight-gradient half of the implicit-GEMM convolution family for gfx950 (its own translation unit: the fprop / dgrad templates of
 // conv_igemm.hip and these compile in parallel). Entry points: mg_conv_wgrad_workspace, mg_conv_wgrad_ws, mg_conv_wgrad.
 #include "common.h"
+#include "launch.h"
 #include "conv_xcd.h"
 #include "conv_forms.h"
 #include "../../include/maggie_hip.h"
@@ -339,9 +340,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(const RedTabl
         if (g_park.on) { g_park.ws = (WS); g_park.n = n; g_park.splits = (int)(SPLITS); g_park.form = RED_FORM_##KERN; g_park.blocks = (long)(B); }    \
         else {                                                                                                                                         \
             MG_FORM(RED_FORM_##KERN == 0 ? MG_FF_REDUCE : RED_FORM_##KERN == 1 ? MG_FF_REDUCE_WAVE : MG_FF_REDUCE_TILE, 0, 0, 0, 0, MG_FORM_NOMODE, 0); \
-            if (p.dw_dtype == MG_BF16) hipLaunchKernelGGL(KERN<bf16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (bf16raw*)p.stats); \
-            else if (p.dw_dtype == MG_F16) hipLaunchKernelGGL(KERN<f16raw>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (f16raw*)p.stats); \
-            else hipLaunchKernelGGL(KERN<float>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, p.stats);                                \
+            MG_WITH_DTYPE(p.dw_dtype, TO, hipLaunchKernelGGL(KERN<TO>, dim3((unsigned)(B)), dim3(256), 0, st, WS, (int)(SPLITS), n, (TO*)p.stats);); \
         }                                                                                                                                              \
     } while (0)
 
@@ -642,7 +641,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_gather9_kernel(const mg_conv_
 }
 
 static inline bool wgrad_gather9_eligible(const mg_conv_params& p) {
-    static const int on = [] { const char* e = getenv("MG_WGRAD_GATHER9"); return e ? atoi(e) : 1; }();
+    static const int on = (int)mg_env_long("MG_WGRAD_GATHER9", 1);
     // Cin >= 64 only: at Cin 32 (the OS1 level: ~20 stages of 64 rows per block, 18 MFMAs per stage) the kernel is bound by the gather latency
     // of its short stages and the per-tap kernel's 128-row steps win (measured 52 -> 64 us); at Cin 64: 55 -> 27, 54 -> 41, 32 -> 23 us
     return on && MG_IS16(p.dtype) && p.mode == MG_MODE_GATHER && p.nbr && p.R * p.S == 9 && p.Cin % 64 == 0 && p.Cout % 32 == 0 &&
@@ -650,8 +649,8 @@ static inline bool wgrad_gather9_eligible(const mg_conv_params& p) {
 }
 static long plan_wgrad_gather9(const mg_conv_params& p) {
     // ~512 workgroups (two fit a CU), bounded by ~20 MB of fp32 partial slabs (written once, read once by the reduce)
-    static const long target = [] { const char* e = getenv("MG_WGRAD_GATHER_BLOCKS"); return e ? atol(e) : 512l; }();
-    static const long ws_cap = [] { const char* e = getenv("MG_WGRAD_GATHER_WS_MB"); return (e ? atol(e) : 20l) << 18; }();   // floats
+    static const long target = mg_env_long("MG_WGRAD_GATHER_BLOCKS", 512l);
+    static const long ws_cap = mg_env_long("MG_WGRAD_GATHER_WS_MB", 20l) << 18;   // floats
     const int tco = p.Cout % 64 == 0 ? 64 : 32;
     const long cc = (long)(p.Cout / tco) * (p.Cin / 32);
     const long n = (long)p.Cout * 9 * p.Cin;
@@ -670,32 +669,19 @@ static int launch_wgrad_gather9(const mg_conv_params& p, float* ws, long ws_floa
     const long cc = (long)(p.Cout / tco) * (p.Cin / 32);
     dim3 grid(xcd_grid(splits * cc));
     const size_t lds = (size_t)(64 * (tco + 16) + 9 * 64 * (32 + 16)) * sizeof(bf16raw);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<1, f16raw>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<2, f16raw>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        attr_set = true;
-    }
-    if (p.xf_scale) {                                        // x = a raw conv output, BatchNorm1d + activation applied on the way into LDS
+    // (the plain forms first: the kernels leave the compiler in the order in which the launcher names them, and that order is kept as it was)
+    if (!p.xf_scale) {
+        MG_FORM(MG_FF_WGRAD_GATHER9, tco / 32, 0, 0, 0, MG_FORM_NOMODE, 0);
+        if (p.dtype != MG_F16) {
+            if (tco != 64) MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<1>), grid, dim3(256), lds, st, p, (int)splits, ws);
+            else MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<2>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        } else if (tco != 64) MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<1, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        else MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<2, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
+    } else {                                                 // x = a raw conv output, BatchNorm1d + activation applied on the way into LDS
         if (tco != 32) return MG_XF_UNSUPPORTED;
         MG_FORM(MG_FF_WGRAD_GATHER9, 1, 0, 0, 0, MG_FORM_NOMODE, MG_FORM_XF);
-        static bool xattr = false;
-        if (!xattr) {
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<1, bf16raw, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            (void)hipFuncSetAttribute((const void*)igemm_wgrad_gather9_kernel<1, f16raw, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-            xattr = true;
-        }
-        if (p.dtype == MG_F16) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, f16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
-        else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, bf16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
-    } else {
-        MG_FORM(MG_FF_WGRAD_GATHER9, tco / 32, 0, 0, 0, MG_FORM_NOMODE, 0);
-        if (p.dtype == MG_F16) {
-            if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
-            else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1, f16raw>), grid, dim3(256), lds, st, p, (int)splits, ws);
-        } else if (tco == 64) hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<2>), grid, dim3(256), lds, st, p, (int)splits, ws);
-        else hipLaunchKernelGGL((igemm_wgrad_gather9_kernel<1>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        if (p.dtype != MG_F16) MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<1, bf16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
+        else MG_LAUNCH_LDS((igemm_wgrad_gather9_kernel<1, f16raw, true>), grid, dim3(256), lds, st, p, (int)splits, ws);
     }
     if (splits >= 8) {
         const long b = (n + 31) / 32;
@@ -806,7 +792,7 @@ __global__ __launch_bounds__(256) void igemm_wgrad_c8_kernel(const mg_conv_param
 }
 
 static inline bool wgrad_c8_eligible(const mg_conv_params& p) {
-    static const int on = [] { const char* e = getenv("MG_WGRAD_C8"); return e ? atoi(e) : 1; }();
+    static const int on = (int)mg_env_long("MG_WGRAD_C8", 1);
     return on && MG_IS16(p.dtype) && p.mode == MG_MODE_CONV && !p.m_dev && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.dil == 1 &&
            p.Hout == p.Hin && p.Wout == p.Win && p.Cin == 8 && p.Cout % 32 == 0 && p.ldx % 8 == 0 && p.ldy % 8 == 0 && p.yoff % 8 == 0 &&
            p.Wout >= 16 && p.Hout >= 8;
@@ -840,7 +826,7 @@ static int launch_wgrad_c8(const mg_conv_params& p, float* ws, long ws_floats, h
 }
 
 static inline bool wgrad_halo_eligible(const mg_conv_params& p) {
-    static const int on = [] { const char* e = getenv("MG_WGRAD_HALO"); return e ? atoi(e) : 1; }();
+    static const int on = (int)mg_env_long("MG_WGRAD_HALO", 1);
     return on && MG_IS16(p.dtype) && p.mode == MG_MODE_CONV && !p.m_dev && p.R == 3 && p.S == 3 && p.stride == 1 && p.pad == 1 && p.dil == 1 &&
            p.Hout == p.Hin && p.Wout == p.Win && p.Cin % 32 == 0 && p.Cout % 32 == 0 && p.ldx % 8 == 0 && p.ldy % 8 == 0 && p.yoff % 8 == 0 &&
            p.Wout >= 16 && p.Hout >= 8 && (long)p.Cout * 9 * p.Cin <= (16l << 20);
@@ -854,7 +840,7 @@ static WgradHaloPlan plan_wgrad_halo(const mg_conv_params& p) {
     // ~one workgroup per CU: with the slab reductions parked (mg_conv_wgrad_park) the slabs come back from HBM, not from the Infinity Cache, and
     // every spatial split is 36 KB per (co, ci) tile written and read once more -- 256 against 512: 11.61 against 11.70 ms per step (3 x 200-step
     // pairs on one lease; 128: 11.83)
-    static const long target = [] { const char* e = getenv("MG_WGRAD_HALO_BLOCKS"); return e ? atol(e) : 256l; }();
+    static const long target = mg_env_long("MG_WGRAD_HALO_BLOCKS", 256l);
     const long n = (long)p.Cout * 9 * p.Cin;
     long splits = (target + cc - 1) / cc;
     if (splits > S) splits = S;
@@ -906,12 +892,12 @@ WgradPlan plan_wgrad(const mg_conv_params& p) {
     const long tiles = (long)taps * nci * nco;
     // design point: ~8 row steps per block (amortises the tile epilogue), bounded by ~2048 blocks, 512 splits and a 64 MB
     // partial-tile workspace; never fewer blocks than ~1 per CU when the rows allow it
-    static const long target = [] { const char* e = getenv("MG_WGRAD_BLOCKS"); return e ? atol(e) : 256l; }();
+    static const long target = mg_env_long("MG_WGRAD_BLOCKS", 256l);
     const long n = (long)p.Cout * taps * p.Cin;
     long splits = p.M / (8 * KSTEP);
     // once the rows are split anyway (a reduce pass exists), ~3 blocks per CU hide more latency: +8 % on the C128 / C256 layers;
     // a layer that fits one split stays unsplit (no workspace round trip)
-    static const long target_split = [] { const char* e = getenv("MG_WGRAD_BLOCKS_SPLIT"); return e ? atol(e) : 768l; }();
+    static const long target_split = mg_env_long("MG_WGRAD_BLOCKS_SPLIT", 768l);
     long lo = ((splits > 1 ? target_split : target) + tiles - 1) / tiles;
     long by_rows = (p.M + 2 * KSTEP - 1) / (2 * KSTEP);           // at least 2 steps per block
     if (lo > by_rows) lo = by_rows;
@@ -922,7 +908,7 @@ WgradPlan plan_wgrad(const mg_conv_params& p) {
     if (p.m_dev) {
         // sparse head: M is the CAPACITY (every site of the frame); the live rows are typically 10-20 % of it and are divided evenly over the
         // splits in-kernel, so a capacity-sized split count only buys zero slabs (33 MB written + 33 MB re-read per C64 launch; step time 15.20 / 15.10 / 15.10 / 15.18 ms at 512 / 128 / 64 / 32)
-        static const long dev_splits = [] { const char* e = getenv("MG_WGRAD_DEV_SPLITS"); return e ? atol(e) : 128l; }();
+        static const long dev_splits = mg_env_long("MG_WGRAD_DEV_SPLITS", 128l);
         const long cap = (dev_splits * 9 + tiles - 1) / tiles;            // ~dev_splits row ranges for a 3x3 layer's 9 tap tiles
         if (splits > cap) splits = cap;
     }
@@ -1059,9 +1045,7 @@ extern "C" int mg_conv_wgrad_ws(const mg_conv_params* pp, float* workspace, long
     if (!pp->stats) return -4;
     if (pp->M <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (pp->dtype == MG_BF16) return dispatch_wgrad<bf16raw>(*pp, workspace, workspace_floats, nullptr, st);
-    if (pp->dtype == MG_F16) return dispatch_wgrad<f16raw>(*pp, workspace, workspace_floats, nullptr, st);
-    return dispatch_wgrad<float>(*pp, workspace, workspace_floats, nullptr, st);
+    MG_WITH_DTYPE(pp->dtype, T, return dispatch_wgrad<T>(*pp, workspace, workspace_floats, nullptr, st));
 }
 
 extern "C" int mg_conv_wgrad(const mg_conv_params* pp, void* stream) { return mg_conv_wgrad_ws(pp, nullptr, 0, stream); }

@@ -14,12 +14,12 @@
 // issued back to back on the same stream -- also inside a captured graph, where stream order becomes a dependency edge. Kernels of
 // this library that run CONCURRENTLY on several streams (MAGGIE_BRANCHES, MAGGIE_SIDE_WGRAD: both off by default) must not use it.
 #include "common.h"
+#include "launch_host.h"
 #include "../../include/maggie_hip.h"
 
 int mg_det_on = 1;
 // One scratch PER DEVICE, allocated once and never freed or moved: captured graphs hold its address (the first version kept a
 // single process-wide buffer and re-allocated it on growth or on a device change, under the feet of graphs captured before).
-constexpr int MG_MAX_DEVICES = 16;
 static char* g_buf[MG_MAX_DEVICES] = {};
 static long g_bytes[MG_MAX_DEVICES] = {};
 static unsigned* g_coop[MG_MAX_DEVICES] = {};     // mg_coop_sync(), below
@@ -50,7 +50,7 @@ extern "C" int mg_det_init(long bytes) {
     g_coop[dev] = (unsigned*)c;
     void* t = nullptr;
     e = hipMalloc(&t, 2 * MG_TAIL_WORDS * 4);
-    if (e != hipSuccess) return (int)e;
+    if (e != hipSuccess) { g_coop[dev] = nullptr; (void)hipFree(c); return (int)e; }
     e = hipMemset(t, 0, 2 * MG_TAIL_WORDS * 4);
     if (e != hipSuccess) return (int)e;
     g_tail[dev] = (unsigned*)t;

@@ -10,6 +10,7 @@
 //   * the backward pass applies the exact adjoints (U^T, D^T with their reflect-border terms) instead of autograd graphs.
 // All kernels are HBM/L2-bound stencils; each block reduces its partial sums before one atomicAdd per sum.
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -544,10 +545,10 @@ inline dim3 grid2(long per_plane, int P, long max_blocks = 1024) {
 }
 // kernels that end with one atomicAdd per sum per block: every block hits the same 2-3 addresses, so keep the block count low
 // (8 planes x 1024 blocks x 3 same-address atomics cost more than the stencil itself)
-static const long REDUCING_BLOCKS_PER_PLANE = [] { const char* e = getenv("MG_LOSS_BLOCKS"); return e ? atol(e) : 256l; }();
+static const long REDUCING_BLOCKS_PER_PLANE = mg_env_long("MG_LOSS_BLOCKS", 256l);
 
 // MG_LOSS_BATCHED (default 1): the batched-load forms of the pyramid / Sobel-adjoint stencils (even plane sizes; odd ones keep the first forms)
-static const int LOSS_BATCHED = [] { const char* e = getenv("MG_LOSS_BATCHED"); return e ? atoi(e) : 1; }();
+static const int LOSS_BATCHED = (int)mg_env_long("MG_LOSS_BATCHED", 1);
 
 static void launch_pyr_lap_fwd(dim3 g, hipStream_t st, const float* x, const float* down, P3 ww, int lvl, int H0, int W0, const int* flags, int h, int w,
                                float* G, float* sums, int Pper, float* slots) {

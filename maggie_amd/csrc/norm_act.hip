@@ -7,6 +7,7 @@
 //   maggie/network/module/aspp.py:34-56; maggie/network/decoder/resnet_inst_matt_spconv.py:69-130.
 #include <stdlib.h>
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -779,9 +780,7 @@ extern "C" int mg_colstats_dev(const void* x, int dtype, int M, int C, int ld, f
     // deterministic mode: MG_DET_STAT_ROWS (1024 >= the row-block count) rows, i.e. one row per row block -- a word receives ONE addition, the
     // finalize kernel adds the rows in index order
     const int nrep = mg_det_on ? MG_DET_STAT_ROWS : MG_STAT_REPLICAS;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(colstats_kernel<bf16raw>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const bf16raw*)x, M, C, ld, stats, g.rpb, nrep, 0, g.tx, g.ty, m_dev, nullptr);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(colstats_kernel<f16raw>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const f16raw*)x, M, C, ld, stats, g.rpb, nrep, 0, g.tx, g.ty, m_dev, nullptr);
-    else hipLaunchKernelGGL(colstats_kernel<float>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const float*)x, M, C, ld, stats, g.rpb, nrep, 0, g.tx, g.ty, m_dev, nullptr);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(colstats_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const T*)x, M, C, ld, stats, g.rpb, nrep, 0, g.tx, g.ty, m_dev, nullptr););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -805,9 +804,7 @@ extern "C" int mg_bias_act_bwd_dev(const void* dy, const void* y, void* g, int d
     const size_t lds = (size_t)gm.ty * gm.tx * ce * sizeof(float);
     float* slots = nullptr;
     if (db && mg_det_on && gm.rb > 1) { slots = mg_det_scratch_on((long)gm.rb * C, st); if (!slots) return MG_DET_NO_SCRATCH; }
-    if (dtype == MG_BF16) hipLaunchKernelGGL(bias_act_bwd_kernel<bf16raw>, dim3(gm.rb, gm.groups), dim3(NT), lds, st, (const bf16raw*)dy, (const bf16raw*)y, (bf16raw*)g, M, C, db, gm.rpb, gm.tx, gm.ty, m_dev, slots);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(bias_act_bwd_kernel<f16raw>, dim3(gm.rb, gm.groups), dim3(NT), lds, st, (const f16raw*)dy, (const f16raw*)y, (f16raw*)g, M, C, db, gm.rpb, gm.tx, gm.ty, m_dev, slots);
-    else hipLaunchKernelGGL(bias_act_bwd_kernel<float>, dim3(gm.rb, gm.groups), dim3(NT), lds, st, (const float*)dy, (const float*)y, (float*)g, M, C, db, gm.rpb, gm.tx, gm.ty, m_dev, slots);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(bias_act_bwd_kernel<T>, dim3(gm.rb, gm.groups), dim3(NT), lds, st, (const T*)dy, (const T*)y, (T*)g, M, C, db, gm.rpb, gm.tx, gm.ty, m_dev, slots););
     MG_CHECK_LAUNCH();
     if (slots) return mg_det_reduce1(slots, gm.rb, db, C, st);
     return 0;
@@ -829,19 +826,14 @@ extern "C" int mg_colstats_centered_dev(const void* x, int dtype, int M, int C, 
     // Deterministic mode: each pass stores one partial row per row block, mg_det_reduce adds them in order (two more small launches).
     float* slots = nullptr;
     if (mg_det_on && g.rb > 1) { slots = mg_det_scratch_on((long)g.rb * C, st); if (!slots) return MG_DET_NO_SCRATCH; }
-#define MG_CENTERED_CASE(T)                                                                                                                              \
-    do {                                                                                                                                                 \
-        if (!have_sum) {                                                                                                                                 \
-            hipLaunchKernelGGL(colstats_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const T*)x, M, C, ld, stats, g.rpb, 1, 1, g.tx, g.ty, m_dev, slots); \
-            if (slots) { int rc_ = mg_det_reduce1(slots, g.rb, stats, C, st); if (rc_) return rc_; }                                                    \
-        }                                                                                                                                                \
-        hipLaunchKernelGGL(colstats_centered_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const T*)x, M, C, ld, stats, g.rpb, g.tx, g.ty, m_dev, slots); \
-        if (slots) { int rc_ = mg_det_reduce1(slots, g.rb, stats + C, C, st); if (rc_) return rc_; }                                                    \
-    } while (0)
-    if (dtype == MG_BF16) MG_CENTERED_CASE(bf16raw);
-    else if (dtype == MG_F16) MG_CENTERED_CASE(f16raw);
-    else MG_CENTERED_CASE(float);
-#undef MG_CENTERED_CASE
+    MG_WITH_DTYPE(dtype, T,
+        if (!have_sum) {
+            hipLaunchKernelGGL(colstats_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const T*)x, M, C, ld, stats, g.rpb, 1, 1, g.tx, g.ty, m_dev, slots);
+            if (slots) { int rc_ = mg_det_reduce1(slots, g.rb, stats, C, st); if (rc_) return rc_; }
+        }
+        hipLaunchKernelGGL(colstats_centered_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, st, (const T*)x, M, C, ld, stats, g.rpb, g.tx, g.ty, m_dev, slots);
+        if (slots) { int rc_ = mg_det_reduce1(slots, g.rb, stats + C, C, st); if (rc_) return rc_; }
+    );
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -897,9 +889,7 @@ extern "C" int mg_affine_act(const mg_rowwise_params* p, void* stream) {
     if (p->M <= 0) return 0;
     const int ce = MG_IS16(p->dtype) ? 8 : 4;
     long total = (long)p->M * (p->C / ce);
-    if (p->dtype == MG_BF16) hipLaunchKernelGGL(affine_act_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
-    else if (p->dtype == MG_F16) hipLaunchKernelGGL(affine_act_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(affine_act_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
+    MG_WITH_DTYPE(p->dtype, T, hipLaunchKernelGGL(affine_act_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -909,7 +899,7 @@ extern "C" int mg_affine_act(const mg_rowwise_params* p, void* stream) {
 // kernel boundary it removes. Same verdict as the flag hand-shake of bn_bwd_coop_kernel: on this part a cross-workgroup meeting point
 // inside a launch is dearer than a kernel boundary, with or without waiting. Kept for the tests and as the measured answer to "let the last block of
 // the reduction do the ordered sum" (VERDICT round 5, item 4a): mg_set_bn_bwd_tail / MG_BN_BWD_TAIL=1.
-static int g_bn_bwd_tail = [] { const char* e = getenv("MG_BN_BWD_TAIL"); return e ? atoi(e) : 0; }();
+static int g_bn_bwd_tail = (int)mg_env_long("MG_BN_BWD_TAIL", 0);
 extern "C" int mg_set_bn_bwd_tail(int on) { const int was = g_bn_bwd_tail; g_bn_bwd_tail = on ? 1 : 0; return was; }
 
 // `hand_over` (deterministic mode): when the partial rows number at most `hand_over_max`, they are NOT summed here -- *hand_over receives
@@ -922,12 +912,12 @@ static int bn_bwd_reduce_impl(const mg_rowwise_params* p, void* stream, float** 
     // row blocks: every block ends with one atomic per channel, all blocks on the same 2C addresses -- past ~256 blocks those serialise into a
     // tail longer than what the extra parallelism buys, except on the largest tensors (measured, us at 128 / 256 / 512 / 1024 row blocks:
     // 1M x 32: 109 / 60 / 45 / 52; 262144 x 64: 56 / 35 / 31 / 43; 262144 x 32: 29 / 21.5 / 24 / 36; 65536 x 64: 19 / 13 / 19 / 19)
-    static const int env_rb = [] { const char* e = getenv("MG_BN_RB"); return e ? atoi(e) : 0; }();
+    static const int env_rb = (int)mg_env_long("MG_BN_RB", 0);
     const int max_rb = env_rb > 0 ? env_rb : ((long)p->M * p->C >= (16l << 20) ? 512 : 256);
     ColGeom g = col_geom(p->M, p->C, ce, max_rb);
     // the row-block count is capped by the atomics, not by the work: when a block still walks >= 256 rows, 1024-thread blocks put four times the
     // waves (loads in flight) behind the same number of atomics (65536 x 64..128: 18.6 us with 4 waves per CU, the tensor is 16-32 MB)
-    static const int wide_on = [] { const char* e = getenv("MG_BN_WIDE"); return e ? atoi(e) : 1; }();
+    static const int wide_on = (int)mg_env_long("MG_BN_WIDE", 1);
     const bool wide = wide_on && !p->m_dev && max_rb == 256 && g.rpb >= 256 && (g.tx & (g.tx - 1)) == 0;      // (the >= 16 M element layers: 25 -> 36 us)
     if (wide) g = col_geom(p->M, p->C, ce, max_rb, 1024, 2);
     const size_t lds = wide ? (size_t)16 * g.tx * 2 * ce * sizeof(float) : (size_t)g.ty * g.tx * 2 * ce * sizeof(float);
@@ -939,12 +929,8 @@ static int bn_bwd_reduce_impl(const mg_rowwise_params* p, void* stream, float** 
     if (g_bn_bwd_tail && slots && !(hand_over && g.rb <= hand_over_max) && g.groups <= MG_TAIL_WORDS && g.tx * ce * 2 * MG_DET_CHUNKS * sizeof(float) <= lds)
         tail = mg_det_tail_words((hipStream_t)stream);
     if (wide) {
-        if (p->dtype == MG_BF16) hipLaunchKernelGGL((bn_bwd_reduce_kernel<bf16raw, 1024>), dim3(g.rb, g.groups), dim3(1024), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
-        else if (p->dtype == MG_F16) hipLaunchKernelGGL((bn_bwd_reduce_kernel<f16raw, 1024>), dim3(g.rb, g.groups), dim3(1024), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
-        else hipLaunchKernelGGL((bn_bwd_reduce_kernel<float, 1024>), dim3(g.rb, g.groups), dim3(1024), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
-    } else if (p->dtype == MG_BF16) hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16raw>, dim3(g.rb, g.groups), dim3(NT), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
-    else if (p->dtype == MG_F16) hipLaunchKernelGGL(bn_bwd_reduce_kernel<f16raw>, dim3(g.rb, g.groups), dim3(NT), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
-    else hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, dim3(g.rb, g.groups), dim3(NT), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail);
+        MG_WITH_DTYPE(p->dtype, T, hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, 1024>), dim3(g.rb, g.groups), dim3(1024), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail););
+    } else MG_WITH_DTYPE(p->dtype, T, hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(g.rb, g.groups), dim3(NT), lds, (hipStream_t)stream, *p, g.rpb, g.tx, g.ty, slots, tail););
     MG_CHECK_LAUNCH();
     if (tail) return 0;                                        // the last row block of every channel group added the rows itself
     if (slots && hand_over && g.rb <= hand_over_max) { *hand_over = slots; *hand_over_rows = g.rb; return 0; }
@@ -962,7 +948,7 @@ static bool bn_fixed_shape_ok(const mg_rowwise_params& p) {
 static bool bn_fixed_ok(const mg_rowwise_params& p) {
     // the general apply pass stays on the simple grid-stride kernel (8.0 us average against 8.9 us for this one at nrep = 1: more registers,
     // fewer waves in flight); this kernel serves the linked path (replicated sums). MG_BN_FIXED_APPLY=1 uses it everywhere.
-    static const int on = [] { const char* e = getenv("MG_BN_FIXED_APPLY"); return e ? atoi(e) : 0; }();
+    static const int on = (int)mg_env_long("MG_BN_FIXED_APPLY", 0);
     const int ce = MG_IS16(p.dtype) ? 8 : 4;
     const int cpr = p.C / ce;
     return on && p.M > 0 && cpr > 0 && cpr <= NT && (NT % cpr) == 0 && p.ldx % ce == 0 && p.lddy % ce == 0 && (!p.dx || p.lddx % ce == 0) &&
@@ -971,9 +957,7 @@ static bool bn_fixed_ok(const mg_rowwise_params& p) {
 static int bn_bwd_apply_fixed_launch(const mg_rowwise_params& p, const float* sums_rep, int nrep, int premasked, float* sums_out, hipStream_t st) {
     const int ce = MG_IS16(p.dtype) ? 8 : 4;
     const long total = (long)p.M * (p.C / ce);
-    if (p.dtype == MG_BF16) hipLaunchKernelGGL(bn_bwd_apply_fixed_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, sums_rep, nrep, premasked, sums_out);
-    else if (p.dtype == MG_F16) hipLaunchKernelGGL(bn_bwd_apply_fixed_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, sums_rep, nrep, premasked, sums_out);
-    else hipLaunchKernelGGL(bn_bwd_apply_fixed_kernel<float>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, sums_rep, nrep, premasked, sums_out);
+    MG_WITH_DTYPE(p.dtype, T, hipLaunchKernelGGL(bn_bwd_apply_fixed_kernel<T>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, sums_rep, nrep, premasked, sums_out););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -993,9 +977,7 @@ extern "C" int mg_bn_bwd_apply(const mg_rowwise_params* p, void* stream) {
     if (bn_fixed_ok(*p)) return bn_bwd_apply_fixed_launch(*p, p->sums, 1, 0, nullptr, (hipStream_t)stream);
     const int ce = MG_IS16(p->dtype) ? 8 : 4;
     long total = (long)p->M * (p->C / ce);
-    if (p->dtype == MG_BF16) hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
-    else if (p->dtype == MG_F16) hipLaunchKernelGGL(bn_bwd_apply_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
-    else hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p);
+    MG_WITH_DTYPE(p->dtype, T, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, (hipStream_t)stream, *p););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -1277,7 +1259,7 @@ static bool bn_small_ok(const mg_rowwise_params& p) {
     // rows up to which the one-launch form is used: a workgroup reads its 16-byte column slice with a row stride, i.e. one cache line per
     // lane -- at 4096 rows x 32 workgroups that costs as much as the four coalesced launches it replaces (24.8 us forward, 33.7 us backward
     // against ~25 / ~17 us); at 1024 rows (64 workgroups x 4 rows per thread) it is 12 us each way. MG_BN_SMALL_ROWS=0 switches it off.
-    static const int max_rows = [] { const char* e = getenv("MG_BN_SMALL_ROWS"); return e ? atoi(e) : 1024; }();
+    static const int max_rows = (int)mg_env_long("MG_BN_SMALL_ROWS", 1024);
     const int ce = MG_IS16(p.dtype) ? 8 : 4;
     return !p.m_dev && !p.count_ptr && p.M > 1 && p.M <= max_rows && p.M <= 16 * NT && p.C % ce == 0 && p.ldx % ce == 0;
 }
@@ -1307,7 +1289,7 @@ static bool bn_fused_ok(const mg_rowwise_params& p) {
     // off by default: 0.89 ms per step against 0.98 ms for finalize + apply in the kernel trace, but nothing on the step's wall clock (13.48 vs
     // 13.43-13.50 ms over 60-step runs): its register footprint (per-channel constants + the prefetched row) costs the streaming part what the
     // removed launch saved. MG_BN_FUSED_APPLY=1 switches it on.
-    static const int on = [] { const char* e = getenv("MG_BN_FUSED_APPLY"); return e ? atoi(e) : 0; }();
+    static const int on = (int)mg_env_long("MG_BN_FUSED_APPLY", 0);
     const int ce = MG_IS16(p.dtype) ? 8 : 4;
     const int cpr = p.C / ce;
     return on && p.M > 0 && cpr > 0 && cpr <= NT && (NT % cpr) == 0 && p.ldx % ce == 0;
@@ -1317,9 +1299,7 @@ static int bn_apply_fused_launch(const mg_rowwise_params& p, const float* stats,
     const int ce = MG_IS16(p.dtype) ? 8 : 4;
     const long total = (long)p.M * (p.C / ce);
     BnFin f{stats, nrep, centered, gamma, beta, running_mean, running_var, momentum, eps, outs};
-    if (p.dtype == MG_BF16) hipLaunchKernelGGL(bn_apply_fused_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, f);
-    else if (p.dtype == MG_F16) hipLaunchKernelGGL(bn_apply_fused_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, f);
-    else hipLaunchKernelGGL(bn_apply_fused_kernel<float>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, f);
+    MG_WITH_DTYPE(p.dtype, T, hipLaunchKernelGGL(bn_apply_fused_kernel<T>, dim3(grid_for(total)), dim3(NT), (size_t)(NT + 2 * p.C) * sizeof(float), st, p, f););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -1547,7 +1527,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_coop_kernel(const mg_rowwise_params
     }
 }
 
-static int g_bn_coop = [] { const char* e = getenv("MG_BN_COOP"); return e ? atoi(e) : 0; }();
+static int g_bn_coop = (int)mg_env_long("MG_BN_COOP", 0);
 extern "C" int mg_set_bn_coop(int on) { const int was = g_bn_coop; g_bn_coop = on ? 1 : 0; return was; }
 struct CoopPlan { int rb, rpb, keep, groups; };
 // the one-launch form serves 16-bit layers whose rows fit the register file: C % 32 == 0, host row count, rows per thread <= 8
@@ -1599,7 +1579,7 @@ extern "C" int mg_bn_train_bwd(const mg_rowwise_params* p, int sums_zeroed, void
     // MG_BN_BWD_HANDOVER=n: layers with <= n row blocks skip the ordered-sum launch, the apply pass adds the partial rows itself. Off by default:
     // measured 11.97 / 11.77 ms (n = 32) against 11.74 / 11.71 ms (off) on one lease, 12.05 at n = 64 -- every workgroup of the apply pass repeats
     // the row sum in front of its streaming part, which costs what the removed ~6 us launch saved.
-    static const int max_rows = [] { const char* e = getenv("MG_BN_BWD_HANDOVER"); return e ? atoi(e) : 0; }();
+    static const int max_rows = (int)mg_env_long("MG_BN_BWD_HANDOVER", 0);
     float* part = nullptr;
     int nrows = 0;
     const bool can = max_rows > 0 && !p->count_ptr && bn_fixed_shape_ok(*p);
@@ -1616,14 +1596,9 @@ extern "C" int mg_pool2x2(const void* in, void* out, int dtype, int op, int N, i
     int Hi = (op <= 1) ? Ho * 2 : Ho / 2, Wi = (op <= 1) ? Wo * 2 : Wo / 2;
     hipStream_t st = (hipStream_t)stream;
     dim3 g(grid_for(total)), b(NT);
-#define POOL_CASE(T, OP) hipLaunchKernelGGL((pool2x2_kernel<T, OP>), g, b, 0, st, (const T*)in, (T*)out, N, Ho, Wo, C, Hi, Wi)
-    if (dtype == MG_BF16) {
-        switch (op) { case 0: POOL_CASE(bf16raw, 0); break; case 1: POOL_CASE(bf16raw, 1); break; case 2: POOL_CASE(bf16raw, 2); break; case 3: POOL_CASE(bf16raw, 3); break; default: return -2; }
-    } else if (dtype == MG_F16) {
-        switch (op) { case 0: POOL_CASE(f16raw, 0); break; case 1: POOL_CASE(f16raw, 1); break; case 2: POOL_CASE(f16raw, 2); break; case 3: POOL_CASE(f16raw, 3); break; default: return -2; }
-    } else {
-        switch (op) { case 0: POOL_CASE(float, 0); break; case 1: POOL_CASE(float, 1); break; case 2: POOL_CASE(float, 2); break; case 3: POOL_CASE(float, 3); break; default: return -2; }
-    }
+    if (op < 0 || op > 3) return -2;
+#define POOL_CASE(OP) hipLaunchKernelGGL((pool2x2_kernel<T, OP>), g, b, 0, st, (const T*)in, (T*)out, N, Ho, Wo, C, Hi, Wi)
+    MG_WITH_DTYPE(dtype, T, switch (op) { case 0: POOL_CASE(0); break; case 1: POOL_CASE(1); break; case 2: POOL_CASE(2); break; default: POOL_CASE(3); break; });
 #undef POOL_CASE
     MG_CHECK_LAUNCH();
     return 0;
@@ -1675,18 +1650,12 @@ extern "C" int mg_spatial_mean(const void* x, void* out, int dtype, int N, int H
     const int backward = mode == 1;
     const float mul = mode == 2 ? 1.f : 1.f / (float)HW;         // mode 2: the plain sum over the rows (backward of broadcasting one row to HW rows)
     hipStream_t st = (hipStream_t)stream;
-#define MG_SM(T)                                                                                                                                       \
-    do {                                                                                                                                               \
-        if (backward) {                                                                                                                                \
-            long b = ((long)HW * C + 255) / 256; if (b > 1024) b = 1024;                                                                               \
-            hipLaunchKernelGGL(spatial_mean_bwd_kernel<T>, dim3((unsigned)b, N), dim3(256), 0, st, (const T*)x, HW, C, (T*)out);                       \
-        } else hipLaunchKernelGGL(spatial_mean_fwd_kernel<T>, dim3((C + 63) / 64, N), dim3(256), 0, st, (const T*)x, HW, C, ld, mul, (T*)out);         \
-    } while (0)
-    if (dtype == MG_BF16) MG_SM(bf16raw);
-    else if (dtype == MG_F16) MG_SM(f16raw);
-    else if (dtype == MG_F32) MG_SM(float);
-    else return -3;
-#undef MG_SM
+    MG_WITH_DTYPE_OR(dtype, -3, T,
+        if (backward) {
+            long b = ((long)HW * C + 255) / 256; if (b > 1024) b = 1024;
+            hipLaunchKernelGGL(spatial_mean_bwd_kernel<T>, dim3((unsigned)b, N), dim3(256), 0, st, (const T*)x, HW, C, (T*)out);
+        } else hipLaunchKernelGGL(spatial_mean_fwd_kernel<T>, dim3((C + 63) / 64, N), dim3(256), 0, st, (const T*)x, HW, C, ld, mul, (T*)out);
+    );
     MG_CHECK_LAUNCH();
     return 0;
 }

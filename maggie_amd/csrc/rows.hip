@@ -7,6 +7,7 @@
 // here over min(*m_dev, cap) rows, grid-stride from a fixed grid, so that no host code depends on the count and the whole detail
 // stage is a static launch sequence (hipGraph-capturable).
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -246,9 +247,7 @@ extern "C" int mg_rows_sigmoid_mul_fwd(const void* a, int lda, const void* g, vo
     if (M <= 0) return 0;
     const long total = (long)M * (C / (MG_IS16(dtype) ? 8 : 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(sigmul_fwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)a, lda, (const bf16raw*)g, (bf16raw*)out, M, C, m_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(sigmul_fwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)a, lda, (const f16raw*)g, (f16raw*)out, M, C, m_dev);
-    else hipLaunchKernelGGL(sigmul_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)a, lda, (const float*)g, (float*)out, M, C, m_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(sigmul_fwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)a, lda, (const T*)g, (T*)out, M, C, m_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -259,9 +258,7 @@ extern "C" int mg_rows_sigmoid_mul_bwd(const void* dout, const void* a, int lda,
     if (M <= 0) return 0;
     const long total = (long)M * (C / (MG_IS16(dtype) ? 8 : 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(sigmul_bwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dout, (const bf16raw*)a, lda, (const bf16raw*)g, (bf16raw*)da, (bf16raw*)dg, M, C, m_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(sigmul_bwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)dout, (const f16raw*)a, lda, (const f16raw*)g, (f16raw*)da, (f16raw*)dg, M, C, m_dev);
-    else hipLaunchKernelGGL(sigmul_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)dout, (const float*)a, lda, (const float*)g, (float*)da, (float*)dg, M, C, m_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(sigmul_bwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)dout, (const T*)a, lda, (const T*)g, (T*)da, (T*)dg, M, C, m_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -271,9 +268,7 @@ extern "C" int mg_rows_add(const void* a, int lda, const void* b, int ldb, void*
     if (M <= 0) return 0;
     const long total = (long)M * (C / (MG_IS16(dtype) ? 8 : 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(rows_add_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)a, lda, (const bf16raw*)b, ldb, (bf16raw*)out, ldo, M, C, m_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(rows_add_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)a, lda, (const f16raw*)b, ldb, (f16raw*)out, ldo, M, C, m_dev);
-    else hipLaunchKernelGGL(rows_add_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)a, lda, (const float*)b, ldb, (float*)out, ldo, M, C, m_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(rows_add_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)a, lda, (const T*)b, ldb, (T*)out, ldo, M, C, m_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -284,9 +279,7 @@ extern "C" int mg_rows_dropout(const void* x, void* y, int dtype, int M, int C, 
     if (!state || p < 0.f || p > 1.f) return -2;
     const long total = (long)M * (C / (MG_IS16(dtype) ? 8 : 4));
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(rows_dropout_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)x, (bf16raw*)y, M, C, p, state, (uint32_t)salt, m_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(rows_dropout_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)x, (f16raw*)y, M, C, p, state, (uint32_t)salt, m_dev);
-    else hipLaunchKernelGGL(rows_dropout_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)x, (float*)y, M, C, p, state, (uint32_t)salt, m_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(rows_dropout_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)x, (T*)y, M, C, p, state, (uint32_t)salt, m_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -305,9 +298,7 @@ extern "C" int mg_rows_add_layernorm_fwd(const void* x, const void* r, const flo
     const int lpr = C / (MG_IS16(dtype) ? 8 : 4), rpb = NT / lpr;
     long blocks = ((long)M + rpb - 1) / rpb; if (blocks > 2048) blocks = 2048;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(add_layernorm_fwd_kernel<bf16raw>, dim3((unsigned)blocks), dim3(NT), 0, st, (const bf16raw*)x, (const bf16raw*)r, gamma, beta, eps, (bf16raw*)y, rstat, M, C, m_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(add_layernorm_fwd_kernel<f16raw>, dim3((unsigned)blocks), dim3(NT), 0, st, (const f16raw*)x, (const f16raw*)r, gamma, beta, eps, (f16raw*)y, rstat, M, C, m_dev);
-    else hipLaunchKernelGGL(add_layernorm_fwd_kernel<float>, dim3((unsigned)blocks), dim3(NT), 0, st, (const float*)x, (const float*)r, gamma, beta, eps, (float*)y, rstat, M, C, m_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(add_layernorm_fwd_kernel<T>, dim3((unsigned)blocks), dim3(NT), 0, st, (const T*)x, (const T*)r, gamma, beta, eps, (T*)y, rstat, M, C, m_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -322,9 +313,7 @@ extern "C" int mg_rows_add_layernorm_bwd(const void* dy, const void* x, const vo
     long blocks = ((long)M + rpb - 1) / rpb; if (blocks > 512) blocks = 512;
     float* slots = nullptr;
     if (mg_det_on) { slots = mg_det_scratch(blocks * 2 * C); if (!slots) return MG_DET_NO_SCRATCH; }
-    if (dtype == MG_BF16) hipLaunchKernelGGL(add_layernorm_bwd_kernel<bf16raw>, dim3((unsigned)blocks), dim3(NT), 0, st, (const bf16raw*)dy, (const bf16raw*)x, (const bf16raw*)r, gamma, rstat, (bf16raw*)dz, dgamma, dbeta, M, C, m_dev, slots);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(add_layernorm_bwd_kernel<f16raw>, dim3((unsigned)blocks), dim3(NT), 0, st, (const f16raw*)dy, (const f16raw*)x, (const f16raw*)r, gamma, rstat, (f16raw*)dz, dgamma, dbeta, M, C, m_dev, slots);
-    else hipLaunchKernelGGL(add_layernorm_bwd_kernel<float>, dim3((unsigned)blocks), dim3(NT), 0, st, (const float*)dy, (const float*)x, (const float*)r, gamma, rstat, (float*)dz, dgamma, dbeta, M, C, m_dev, slots);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(add_layernorm_bwd_kernel<T>, dim3((unsigned)blocks), dim3(NT), 0, st, (const T*)dy, (const T*)x, (const T*)r, gamma, rstat, (T*)dz, dgamma, dbeta, M, C, m_dev, slots););
     MG_CHECK_LAUNCH();
     if (slots) {
         mg_det_seg sg[2] = {{dgamma, C, 0}, {dbeta, C, 0}};

@@ -6,6 +6,7 @@
 //   :221-232 (OS8 gather + instance guidance), :247-251,264-268 (.dense() and the -99 fill),
 //   :303-304,360-362 (bilinear upsample + (tanh+1)/2), maggie/network/encoder/resnet.py:211-229 (mask-ID embedding).
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -571,9 +572,7 @@ extern "C" int mg_gather_rows_dev(const void* dense, int dtype, const int32_t* c
     if (C % ce || ldo % ce || yoff % ce) return -3;
     long total = (long)R * (C / ce);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gather_rows_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dense, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (bf16raw*)out, ldo, yoff, r_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gather_rows_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)dense, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (f16raw*)out, ldo, yoff, r_dev);
-    else hipLaunchKernelGGL(gather_rows_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)dense, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (float*)out, ldo, yoff, r_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)dense, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (T*)out, ldo, yoff, r_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -591,9 +590,7 @@ extern "C" int mg_gather_rows_bwd_dev(const void* dout, int dtype, int ldo, int 
     if (C % ce || ldo % ce || yoff % ce) return -3;
     long total = (long)R * (C / ce);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gather_rows_bwd_kernel<bf16raw>, dim3(grid_for(total) > 512 ? 512 : grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (const bf16raw*)dense, ddense, dmul, r_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gather_rows_bwd_kernel<f16raw>, dim3(grid_for(total) > 512 ? 512 : grid_for(total)), dim3(NT), 0, st, (const f16raw*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (const f16raw*)dense, ddense, dmul, r_dev);
-    else hipLaunchKernelGGL(gather_rows_bwd_kernel<float>, dim3(grid_for(total) > 512 ? 512 : grid_for(total)), dim3(NT), 0, st, (const float*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (const float*)dense, ddense, dmul, r_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_bwd_kernel<T>, dim3(grid_for(total) > 512 ? 512 : grid_for(total)), dim3(NT), 0, st, (const T*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul, mul_ninst, (const T*)dense, ddense, dmul, r_dev););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -613,9 +610,7 @@ extern "C" int mg_gather_rows_dmul_det(const void* dout, int dtype, int ldo, int
     if (R <= 0) return 0;
     float* slots = mg_det_scratch((long)Q * NCH * C);
     if (!slots) return MG_DET_NO_SCRATCH;
-    if (dtype == MG_BF16) hipLaunchKernelGGL((gather_rows_dmul_det_kernel<bf16raw, NCH>), dim3(NCH, Q), dim3(NT), 0, st, (const bf16raw*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul_ninst, (const bf16raw*)dense, slots, r_dev);
-    else if (dtype == MG_F16) hipLaunchKernelGGL((gather_rows_dmul_det_kernel<f16raw, NCH>), dim3(NCH, Q), dim3(NT), 0, st, (const f16raw*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul_ninst, (const f16raw*)dense, slots, r_dev);
-    else hipLaunchKernelGGL((gather_rows_dmul_det_kernel<float, NCH>), dim3(NCH, Q), dim3(NT), 0, st, (const float*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul_ninst, (const float*)dense, slots, r_dev);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL((gather_rows_dmul_det_kernel<T, NCH>), dim3(NCH, Q), dim3(NT), 0, st, (const T*)dout, ldo, yoff, coords, R, n_i, Hd, Wd, C, mul_ninst, (const T*)dense, slots, r_dev););
     MG_CHECK_LAUNCH();
     mg_det_seg sg{dmul, C, (long)C};
     return mg_det_reduce(slots, NCH, Q, C, 0, &sg, 1, st);
@@ -628,9 +623,7 @@ extern "C" int mg_gather_rows_bwd_dense(const void* dout, int dtype, int ldo, in
     long total = (long)N * Hd * Wd * (C / ce);
     if (total <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gather_rows_bwd_dense_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dout, ldo, yoff, (const unsigned long long*)bits, wordoff, n_i, N, Hd, Wd, C, mul, mul_ninst, (bf16raw*)ddense);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gather_rows_bwd_dense_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)dout, ldo, yoff, (const unsigned long long*)bits, wordoff, n_i, N, Hd, Wd, C, mul, mul_ninst, (f16raw*)ddense);
-    else hipLaunchKernelGGL(gather_rows_bwd_dense_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)dout, ldo, yoff, (const unsigned long long*)bits, wordoff, n_i, N, Hd, Wd, C, mul, mul_ninst, (float*)ddense);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_rows_bwd_dense_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)dout, ldo, yoff, (const unsigned long long*)bits, wordoff, n_i, N, Hd, Wd, C, mul, mul_ninst, (T*)ddense););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -648,9 +641,7 @@ extern "C" int mg_scatter_plane_dev(const void* vals, int dtype, int ldv, int co
     if (n <= 0) return 0;
     hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n)), dim3(NT), 0, st, plane, n, fill);
     if (R > 0) {
-        if (dtype == MG_BF16) hipLaunchKernelGGL(scatter_plane_kernel<bf16raw>, dim3(grid_for(R)), dim3(NT), 0, st, (const bf16raw*)vals, ldv, col, coords, R, H, W, plane, r_dev);
-        else if (dtype == MG_F16) hipLaunchKernelGGL(scatter_plane_kernel<f16raw>, dim3(grid_for(R)), dim3(NT), 0, st, (const f16raw*)vals, ldv, col, coords, R, H, W, plane, r_dev);
-        else hipLaunchKernelGGL(scatter_plane_kernel<float>, dim3(grid_for(R)), dim3(NT), 0, st, (const float*)vals, ldv, col, coords, R, H, W, plane, r_dev);
+        MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(scatter_plane_kernel<T>, dim3(grid_for(R)), dim3(NT), 0, st, (const T*)vals, ldv, col, coords, R, H, W, plane, r_dev););
     }
     MG_CHECK_LAUNCH();
     return 0;
@@ -666,9 +657,7 @@ extern "C" int mg_gather_plane_dev(const float* plane, const int32_t* coords, in
                                    const int32_t* r_dev, int zero_rest, void* stream) {
     if (R <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gather_plane_kernel<bf16raw>, dim3(grid_for(R)), dim3(NT), 0, st, plane, coords, R, H, W, (bf16raw*)vals, ldv, col, r_dev, zero_rest);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gather_plane_kernel<f16raw>, dim3(grid_for(R)), dim3(NT), 0, st, plane, coords, R, H, W, (f16raw*)vals, ldv, col, r_dev, zero_rest);
-    else hipLaunchKernelGGL(gather_plane_kernel<float>, dim3(grid_for(R)), dim3(NT), 0, st, plane, coords, R, H, W, (float*)vals, ldv, col, r_dev, zero_rest);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gather_plane_kernel<T>, dim3(grid_for(R)), dim3(NT), 0, st, plane, coords, R, H, W, (T*)vals, ldv, col, r_dev, zero_rest););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -679,9 +668,7 @@ extern "C" int mg_mask_embed(const float* image, const float* masks, const float
     if (total <= 0) return 0;
     if (H % Hm || W % Wm || n_embed > 3) return -2;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(mask_embed_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, image, masks, table, N, H, W, n_m, Hm, Wm, n_embed, (bf16raw*)out);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(mask_embed_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, image, masks, table, N, H, W, n_m, Hm, Wm, n_embed, (f16raw*)out);
-    else hipLaunchKernelGGL(mask_embed_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, image, masks, table, N, H, W, n_m, Hm, Wm, n_embed, (float*)out);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(mask_embed_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, image, masks, table, N, H, W, n_m, Hm, Wm, n_embed, (T*)out););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -698,15 +685,11 @@ extern "C" int mg_mask_embed_bwd(const void* dx, int dtype, const float* masks, 
         if (g > 512) g = 512;
         float* slots = mg_det_scratch((long)g * nv);
         if (!slots) return MG_DET_NO_SCRATCH;
-        if (dtype == MG_BF16) hipLaunchKernelGGL(mask_embed_bwd_det_kernel<bf16raw>, dim3(g), dim3(NT), 0, st, (const bf16raw*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, slots);
-        else if (dtype == MG_F16) hipLaunchKernelGGL(mask_embed_bwd_det_kernel<f16raw>, dim3(g), dim3(NT), 0, st, (const f16raw*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, slots);
-        else hipLaunchKernelGGL(mask_embed_bwd_det_kernel<float>, dim3(g), dim3(NT), 0, st, (const float*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, slots);
+        MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(mask_embed_bwd_det_kernel<T>, dim3(g), dim3(NT), 0, st, (const T*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, slots););
         MG_CHECK_LAUNCH();
         return mg_det_reduce1(slots, g, dtable, nv, st);
     }
-    if (dtype == MG_BF16) hipLaunchKernelGGL(mask_embed_bwd_kernel<bf16raw>, dim3(g), dim3(NT), 0, st, (const bf16raw*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, dtable);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(mask_embed_bwd_kernel<f16raw>, dim3(g), dim3(NT), 0, st, (const f16raw*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, dtable);
-    else hipLaunchKernelGGL(mask_embed_bwd_kernel<float>, dim3(g), dim3(NT), 0, st, (const float*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, dtable);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(mask_embed_bwd_kernel<T>, dim3(g), dim3(NT), 0, st, (const T*)dx, masks, N, H, W, n_m, Hm, Wm, n_embed, dtable););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -725,9 +708,7 @@ extern "C" int mg_upsample_tanh_ex(const void* in, int dtype, long sn, long sc, 
     const long hw = (long)h * w * scale * scale;
     long bx = (hw + NT - 1) / NT; if (bx > 64) bx = 64;
     dim3 grid((unsigned)bx, (unsigned)(N * C));
-    if (dtype == MG_BF16) hipLaunchKernelGGL(upsample_tanh_kernel<bf16raw>, grid, dim3(NT), 0, st, (const bf16raw*)in, sn, sc, sy, sx, N, C, h, w, scale, apply_tanh, out, pscale, any_nonzero);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(upsample_tanh_kernel<f16raw>, grid, dim3(NT), 0, st, (const f16raw*)in, sn, sc, sy, sx, N, C, h, w, scale, apply_tanh, out, pscale, any_nonzero);
-    else hipLaunchKernelGGL(upsample_tanh_kernel<float>, grid, dim3(NT), 0, st, (const float*)in, sn, sc, sy, sx, N, C, h, w, scale, apply_tanh, out, pscale, any_nonzero);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(upsample_tanh_kernel<T>, grid, dim3(NT), 0, st, (const T*)in, sn, sc, sy, sx, N, C, h, w, scale, apply_tanh, out, pscale, any_nonzero););
     MG_CHECK_LAUNCH();
     return 0;
 }

@@ -8,6 +8,7 @@
 // u has A entries, v has B*taps entries (both updated in place, like the reference's `.data` rebinding).
 // Backward:  dW = G / sigma - (<G, W> / sigma^2) * u v^T   with G = dL/d(out) given in the kernels' layout (fp32).
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -174,9 +175,7 @@ extern "C" int mg_spectral_norm(const float* W, float* u, float* v, int A, int B
     if (need < A) need = A;
     int blocks = grid_for(need);
     if ((long)blocks * NT < (Wd > A ? Wd : A)) blocks = (int)(((Wd > A ? Wd : A) + NT - 1) / NT);
-    if (out_dtype == MG_BF16) hipLaunchKernelGGL(sn_finish_kernel<bf16raw>, dim3(blocks), dim3(NT), 0, st, W, t, s, scratch, A, B, taps, transposed, pad_in, u, v, (bf16raw*)out);
-    else if (out_dtype == MG_F16) hipLaunchKernelGGL(sn_finish_kernel<f16raw>, dim3(blocks), dim3(NT), 0, st, W, t, s, scratch, A, B, taps, transposed, pad_in, u, v, (f16raw*)out);
-    else hipLaunchKernelGGL(sn_finish_kernel<float>, dim3(blocks), dim3(NT), 0, st, W, t, s, scratch, A, B, taps, transposed, pad_in, u, v, (float*)out);
+    MG_WITH_DTYPE(out_dtype, T, hipLaunchKernelGGL(sn_finish_kernel<T>, dim3(blocks), dim3(NT), 0, st, W, t, s, scratch, A, B, taps, transposed, pad_in, u, v, (T*)out););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -550,9 +549,7 @@ extern "C" int mg_spectral_norm_batched(const mg_sn_desc* descs, int n_conv, con
     if (n1 > 0) hipLaunchKernelGGL(snb_wt_u_kernel, dim3(n1), dim3(NT), 0, st, descs, (const int4*)items_k1, work_base);
     if (n2 > 0) hipLaunchKernelGGL(snb_w_t_kernel, dim3(n2), dim3(NT), 0, st, descs, (const int4*)items_k2, work_base);
     hipLaunchKernelGGL(snb_norms_kernel, dim3(n_conv), dim3(NT), 0, st, descs, n_conv, work_base);
-    if (out_dtype == MG_BF16) hipLaunchKernelGGL(snb_finish_kernel<bf16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, work_base, (bf16raw*)out_base, (bf16raw*)out_t_base);
-    else if (out_dtype == MG_F16) hipLaunchKernelGGL(snb_finish_kernel<f16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, work_base, (f16raw*)out_base, (f16raw*)out_t_base);
-    else hipLaunchKernelGGL(snb_finish_kernel<float>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, work_base, (float*)out_base, (float*)out_t_base);
+    MG_WITH_DTYPE(out_dtype, T, hipLaunchKernelGGL(snb_finish_kernel<T>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, work_base, (T*)out_base, (T*)out_t_base););
     hipLaunchKernelGGL(snb_vectors_kernel, dim3(n_conv), dim3(NT), 0, st, descs, n_conv, work_base);
     MG_CHECK_LAUNCH();
     return 0;
@@ -567,16 +564,10 @@ extern "C" int mg_spectral_norm_batched_bwd_to(const mg_sn_desc* descs, int n_co
     if (n_conv <= 0) return 0;
     if (!dot_part) return -2;
     hipStream_t st = (hipStream_t)stream;
-    if (g_dtype == MG_BF16) {
-        hipLaunchKernelGGL(snb_bwd_dot_kernel<bf16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, dot_part);
-        hipLaunchKernelGGL(snb_bwd_apply_kernel<bf16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, work_base, dW_base, dWptrs, dot_part);
-    } else if (g_dtype == MG_F16) {
-        hipLaunchKernelGGL(snb_bwd_dot_kernel<f16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, dot_part);
-        hipLaunchKernelGGL(snb_bwd_apply_kernel<f16raw>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, work_base, dW_base, dWptrs, dot_part);
-    } else {
-        hipLaunchKernelGGL(snb_bwd_dot_kernel<float>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, dot_part);
-        hipLaunchKernelGGL(snb_bwd_apply_kernel<float>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, work_base, dW_base, dWptrs, dot_part);
-    }
+    MG_WITH_DTYPE(g_dtype, T,
+        hipLaunchKernelGGL(snb_bwd_dot_kernel<T>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, dot_part);
+        hipLaunchKernelGGL(snb_bwd_apply_kernel<T>, dim3(n3), dim3(NT), 0, st, descs, (const int4*)items_k3, Gptrs, work_base, dW_base, dWptrs, dot_part);
+    );
     MG_CHECK_LAUNCH();
     return 0;
 }

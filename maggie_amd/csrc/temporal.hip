@@ -8,6 +8,7 @@
 //    propagate t -> t+1).
 // All tensors are rows x channels (NHWC) in the compute dtype T; pure HBM streaming, 16 bytes per lane.
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -146,9 +147,7 @@ extern "C" int mg_gru_gate_fwd(const void* rz, const void* x, const void* h, int
     long total; int rc = gru_check(dtype, M, C, &total); if (rc) return rc;
     if (M <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gru_gate_fwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)rz, (const bf16raw*)x, (const bf16raw*)h, M, C, (bf16raw*)xrh);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gru_gate_fwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)rz, (const f16raw*)x, (const f16raw*)h, M, C, (f16raw*)xrh);
-    else hipLaunchKernelGGL(gru_gate_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)rz, (const float*)x, (const float*)h, M, C, (float*)xrh);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gru_gate_fwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)rz, (const T*)x, (const T*)h, M, C, (T*)xrh););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -158,9 +157,7 @@ extern "C" int mg_gru_gate_bwd(const void* dxrh, const void* rz, const void* h, 
     long total; int rc = gru_check(dtype, M, C, &total); if (rc) return rc;
     if (M <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gru_gate_bwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dxrh, (const bf16raw*)rz, (const bf16raw*)h, M, C, (bf16raw*)dx, (bf16raw*)drz, 2 * C, (bf16raw*)dh_part);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gru_gate_bwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)dxrh, (const f16raw*)rz, (const f16raw*)h, M, C, (f16raw*)dx, (f16raw*)drz, 2 * C, (f16raw*)dh_part);
-    else hipLaunchKernelGGL(gru_gate_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)dxrh, (const float*)rz, (const float*)h, M, C, (float*)dx, (float*)drz, 2 * C, (float*)dh_part);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gru_gate_bwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)dxrh, (const T*)rz, (const T*)h, M, C, (T*)dx, (T*)drz, 2 * C, (T*)dh_part););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -169,9 +166,7 @@ extern "C" int mg_gru_out_fwd(const void* rz, const void* cpre, const void* h, i
     long total; int rc = gru_check(dtype, M, C, &total); if (rc) return rc;
     if (M <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gru_out_fwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)rz, (const bf16raw*)cpre, (const bf16raw*)h, M, C, (bf16raw*)hn);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gru_out_fwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)rz, (const f16raw*)cpre, (const f16raw*)h, M, C, (f16raw*)hn);
-    else hipLaunchKernelGGL(gru_out_fwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)rz, (const float*)cpre, (const float*)h, M, C, (float*)hn);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gru_out_fwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)rz, (const T*)cpre, (const T*)h, M, C, (T*)hn););
     MG_CHECK_LAUNCH();
     return 0;
 }
@@ -182,9 +177,7 @@ extern "C" int mg_gru_out_bwd(const void* dhn, const void* rz, const void* cpre,
     long total; int rc = gru_check(dtype, M, C, &total); if (rc) return rc;
     if (M <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == MG_BF16) hipLaunchKernelGGL(gru_out_bwd_kernel<bf16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const bf16raw*)dhn, (const bf16raw*)rz, (const bf16raw*)cpre, (const bf16raw*)h, M, C, (bf16raw*)drz + C, 2 * C, (bf16raw*)dc_pre, (bf16raw*)dh_part);
-    else if (dtype == MG_F16) hipLaunchKernelGGL(gru_out_bwd_kernel<f16raw>, dim3(grid_for(total)), dim3(NT), 0, st, (const f16raw*)dhn, (const f16raw*)rz, (const f16raw*)cpre, (const f16raw*)h, M, C, (f16raw*)drz + C, 2 * C, (f16raw*)dc_pre, (f16raw*)dh_part);
-    else hipLaunchKernelGGL(gru_out_bwd_kernel<float>, dim3(grid_for(total)), dim3(NT), 0, st, (const float*)dhn, (const float*)rz, (const float*)cpre, (const float*)h, M, C, (float*)drz + C, 2 * C, (float*)dc_pre, (float*)dh_part);
+    MG_WITH_DTYPE(dtype, T, hipLaunchKernelGGL(gru_out_bwd_kernel<T>, dim3(grid_for(total)), dim3(NT), 0, st, (const T*)dhn, (const T*)rz, (const T*)cpre, (const T*)h, M, C, (T*)drz + C, 2 * C, (T*)dc_pre, (T*)dh_part););
     MG_CHECK_LAUNCH();
     return 0;
 }

@@ -7,6 +7,7 @@
 //   mg_token_sa_fwd/bwd : softmax(q k^T / sqrt(d), key padding mask) v for the T tokens of each batch element
 // fp32 throughout (the reference keeps these tiny operands in fp32 too). Any row count; K a multiple of 4.
 #include "common.h"
+#include "launch.h"
 #include "../../include/maggie_hip.h"
 
 namespace {
@@ -727,8 +728,7 @@ extern "C" int mg_token_linear_fwd_ex(const float* x, const float* xadd, const f
     if (gamma && (!beta || !z || !rstat)) return -2;
     const size_t lds = ((size_t)RB * (K + N) + (size_t)K * (N + 1)) * sizeof(float);
     if (lds > 150 * 1024) return -3;
-    static bool attr_f = false;
-    if (!attr_f) { (void)hipFuncSetAttribute((const void*)token_linear_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr_f = true; }
+    MG_RETURN_IF(mg_lds_opt_in<token_linear_fwd_kernel>(lds, 150 * 1024));
     hipLaunchKernelGGL(token_linear_fwd_kernel, dim3((R + RB - 1) / RB), dim3(NT), lds, (hipStream_t)stream, x, xadd, W, bias, res, relu, gamma, beta, eps, y, z,
                        rstat, R, K, N, wt);
     MG_CHECK_LAUNCH();
@@ -754,8 +754,7 @@ extern "C" int mg_token_linear_bwd_ex(const float* dy, const float* x, const flo
     const size_t lds_r = ((size_t)RB * N + (size_t)N * K) * sizeof(float);
     const size_t lds_c = (size_t)32 * (CB + K) * sizeof(float);
     if (lds_r > 150 * 1024) return -3;
-    static bool attr_b = false;
-    if (!attr_b) { (void)hipFuncSetAttribute((const void*)token_linear_bwd_main_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr_b = true; }
+    MG_RETURN_IF(mg_lds_opt_in<token_linear_bwd_main_kernel>(dx ? (lds_r > lds_c ? lds_r : lds_c) : lds_c, 150 * 1024));
     hipStream_t st = (hipStream_t)stream;
     // a plain linear layer (no LayerNorm, no ReLU) has dz == dy: the caller passes dz = dy (and takes dy as the residual gradient) and the dz
     // kernel is skipped
@@ -772,7 +771,7 @@ extern "C" int mg_token_sa_fwd(const float* q, const float* k, const float* v, c
                                float* prob, void* stream) {
     if (B <= 0) return 0;
     if (T <= 0 || T > 16 || D <= 0) return -3;
-    static const int lds_on = [] { const char* e = getenv("MG_TOKEN_SA_LDS"); return e ? atoi(e) : 1; }();
+    static const int lds_on = (int)mg_env_long("MG_TOKEN_SA_LDS", 1);
     if (lds_on && T <= SA_MAXT && D <= SA_MAXD && T * D <= 8 * NT)
         hipLaunchKernelGGL(token_sa_fwd_lds_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, q, k, v, pad, scale, T, D, out, prob);
     else
@@ -785,7 +784,7 @@ extern "C" int mg_token_sa_bwd(const float* dout, const float* q, const float* k
                                float* dq, float* dk, float* dv, void* stream) {
     if (B <= 0) return 0;
     if (T <= 0 || T > 16 || D <= 0) return -3;
-    static const int lds_on = [] { const char* e = getenv("MG_TOKEN_SA_LDS"); return e ? atoi(e) : 1; }();
+    static const int lds_on = (int)mg_env_long("MG_TOKEN_SA_LDS", 1);
     if (lds_on && T <= SA_MAXT && D <= SA_MAXD && T * D <= 8 * NT)
         hipLaunchKernelGGL(token_sa_bwd_lds_kernel, dim3(B), dim3(NT), 0, (hipStream_t)stream, dout, q, k, v, prob, scale, T, D, dq, dk, dv);
     else
@@ -803,9 +802,7 @@ extern "C" int mg_token_einsum_fwd(const void* feat, int dtype, const float* tok
     dim3 grid((L + NT - 1) / NT, B);
     hipStream_t st = (hipStream_t)stream;
 #define EINSUM_FWD(T, CC) hipLaunchKernelGGL((token_einsum_fwd_kernel<T, CC>), grid, dim3(NT), 0, st, (const T*)feat, tok, L, Q, QP, (T*)out)
-    if (dtype == MG_BF16) { if (C == 32) EINSUM_FWD(bf16raw, 32); else EINSUM_FWD(bf16raw, 64); }
-    else if (dtype == MG_F16) { if (C == 32) EINSUM_FWD(f16raw, 32); else EINSUM_FWD(f16raw, 64); }
-    else { if (C == 32) EINSUM_FWD(float, 32); else EINSUM_FWD(float, 64); }
+    MG_WITH_DTYPE(dtype, T, if (C == 32) EINSUM_FWD(T, 32); else EINSUM_FWD(T, 64););
 #undef EINSUM_FWD
     MG_CHECK_LAUNCH();
     return 0;
@@ -823,9 +820,7 @@ extern "C" int mg_token_einsum_bwd(const void* dlog, const void* feat, int dtype
     float* slots = nullptr;
     if (mg_det_on && grid.x > 1) { slots = mg_det_scratch((long)B * grid.x * Q * C); if (!slots) return MG_DET_NO_SCRATCH; }
 #define EINSUM_BWD(T, CC) hipLaunchKernelGGL((token_einsum_bwd_kernel<T, CC>), grid, dim3(NT), 0, st, (const T*)dlog, (const T*)feat, tok, L, Q, QP, (T*)dfeat, dtok, slots)
-    if (dtype == MG_BF16) { if (C == 32) EINSUM_BWD(bf16raw, 32); else EINSUM_BWD(bf16raw, 64); }
-    else if (dtype == MG_F16) { if (C == 32) EINSUM_BWD(f16raw, 32); else EINSUM_BWD(f16raw, 64); }
-    else { if (C == 32) EINSUM_BWD(float, 32); else EINSUM_BWD(float, 64); }
+    MG_WITH_DTYPE(dtype, T, if (C == 32) EINSUM_BWD(T, 32); else EINSUM_BWD(T, 64););
 #undef EINSUM_BWD
     MG_CHECK_LAUNCH();
     if (slots) {
@@ -846,7 +841,7 @@ extern "C" int mg_imd_prep(const float* mask, int n_in, int s, const float* gt, 
     hipError_t e = mg_zero_words(valid, ((long)B * n_i + 3) / 4, st);          // `valid` must be padded to a multiple of 4 bytes by the caller
     if (e != hipSuccess) return (int)e;
     const long cells = (long)B * NF * h * w;
-    static const int planes_on = [] { const char* e = getenv("MG_IMD_PREP_PLANES"); return e ? atoi(e) : 1; }();
+    static const int planes_on = (int)mg_env_long("MG_IMD_PREP_PLANES", 1);
     if (planes_on && gt && guidance && gs == 8 && n_in >= 1 && n_in <= 16 && (s == 1 || s == 2)) {
         const dim3 grid((unsigned)((cells + NT - 1) / NT), (unsigned)(1 + n_i));
         if (s == 1) hipLaunchKernelGGL((imd_prep_planes_kernel<1, 8>), grid, dim3(NT), 0, st, mask, n_in, gt, n_gt, B, NF, h, w, n_i, feat_ids, guidance, valid);
@@ -896,8 +891,7 @@ extern "C" int mg_token_linear_multi_fwd(const mg_tok_lin* ops, int n, void* str
         const int g = (ops[i].R + RB - 1) / RB; if (g > gx) gx = g;
     }
     if (lds > 150 * 1024) return -3;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)token_linear_multi_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = true; }
+    MG_RETURN_IF(mg_lds_opt_in<token_linear_multi_fwd_kernel>(lds, 150 * 1024));
     hipLaunchKernelGGL(token_linear_multi_fwd_kernel, dim3(gx, n), dim3(NT), lds, (hipStream_t)stream, set);
     MG_CHECK_LAUNCH();
     return 0;
@@ -919,8 +913,7 @@ extern "C" int mg_token_linear_multi_bwd(const mg_tok_lin* ops, int n, void* str
         if (o.gamma || o.relu || o.dz != o.dy || o.dres) need_dz = true;
     }
     if (lds > 150 * 1024) return -3;
-    static bool attr = false;
-    if (!attr) { (void)hipFuncSetAttribute((const void*)token_linear_multi_bwd_main_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = true; }
+    MG_RETURN_IF(mg_lds_opt_in<token_linear_multi_bwd_main_kernel>(lds, 150 * 1024));
     if (need_dz) hipLaunchKernelGGL(token_linear_multi_dz_kernel, dim3(gz, n), dim3(NT), 0, st, set);
     hipLaunchKernelGGL(token_linear_multi_bwd_main_kernel, dim3(gx, n), dim3(NT), lds, st, set);
     MG_CHECK_LAUNCH();

@@ -132,3 +132,30 @@ def test_deterministic_mode_is_on():
     from maggie_amd import hip
     _dev()
     assert hip.DETERMINISTIC
+
+
+def test_large_lds_forms_on_a_second_device():
+    """ARMS ITSELF with >= 2 GPUs (skipped on one). The dynamic-LDS opt-in and the CU count are kept per (kernel, device): in a fresh process
+    (tests/second_device_worker.py) the smallest exact-integer case of four forms runs on cuda:0 and then on cuda:1 -- every call returns 0 and
+    holds its expectation on both devices -- and a 66 KiB token-linear launch gives the same bits on both. What each leg exercises there:
+    `h3<8,64,3>` and `async<128,128,2,3>` ask for more than 64 KiB and opt in on the second device, as does the token launch; `h3_slab` asks for
+    less and checks the per-device CU count that sizes its grid; `wgrad_gather9<1>` asks for 60 KiB (the <2> form for exactly 64 KiB), so it
+    opts in nowhere and checks only that the launcher runs on a second device without the 80 KiB requests it used to make."""
+    import json
+    import os
+    import subprocess
+    import sys
+    _dev()
+    if torch.cuda.device_count() < 2:
+        pytest.skip('needs two GPUs: the per-device LDS opt-in stays unexecuted on a second device on this box')
+    worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'second_device_worker.py')
+    forms = ('h3<8,64,3>/CONV', 'h3_slab/CONV', 'async<128,128,2,3>/CONV', 'wgrad_gather9<1>')
+    p = subprocess.run([sys.executable, worker, '0,1'] + list(forms), capture_output=True, text=True, timeout=300)
+    line = [l for l in p.stdout.splitlines() if l.startswith('RESULT ')]
+    assert line, (p.returncode, p.stderr[-3000:])
+    r = json.loads(line[-1][7:])
+    assert p.returncode == 0 and 'error' not in r, (r, p.stderr[-3000:])
+    for form in forms:
+        for d in (0, 1):
+            assert r.get('%s@%d' % (form, d)) == 'ok', r
+    assert r['token_equal'] is True, r

@@ -200,8 +200,11 @@ __device__ __forceinline__ void token_linear_bwd_rows(float* sm, int rblock, con
     __syncthreads();
     const int cols = K < 128 ? K : 128;
     const int c = t % cols, h = t / cols, groups = NT / cols;
+    // threads t >= cols * groups (64 < K < 128: NT is no multiple of cols) take no element: with h >= groups they would walk rows that the threads
+    // of h - groups own as well, and the ADD form's read-modify-write of one element from two waves adds acc once or twice
+    const int rl0 = h < groups ? h : nr;
     for (int k = c; k < K; k += cols) {
-        for (int rl = h; rl < nr; rl += groups) {
+        for (int rl = rl0; rl < nr; rl += groups) {
             float acc = 0.f;
             const float* g = sdz + rl * N;
 #pragma unroll 8

@@ -897,6 +897,29 @@ def attn_feat_bwd(dout, p, feat, kq, vp, ids, scale, NID, want_bias, tn=False):
     return dfeat, dkq, dvp, db2, dob
 
 
+def imd_prep(mask, gt, h, w, n_i):
+    """Mask pre-processing of the instance matte decoder (mg_imd_prep). mask (B, NF, n_in, h*s, w*s) fp32 contiguous, gt (B, NF, n_gt, h*gs, w*gs) fp32
+    contiguous or None -> feat_ids (B, NF*h*w) int32, guidance (B, n_i, NF*h*w) fp32 (None without gt), valid (B, n_i) uint8 (a view of a buffer
+    padded to whole 4-byte words, which the callee clears)."""
+    B, NF, n_in = mask.shape[:3]
+    s = mask.shape[-1] // w
+    if s < 1 or mask.shape[-1] != w * s or mask.shape[-2] != h * s:
+        raise hip.MaggieHipError('imd_prep: the guidance mask must be an integer multiple of the OS8 map (%dx%d), got %dx%d'
+                                 % (h, w, mask.shape[-2], mask.shape[-1]))
+    gs = 1
+    if gt is not None:
+        gs = gt.shape[-1] // w
+        if gs < 1 or gt.shape[-1] != w * gs or gt.shape[-2] != h * gs:
+            raise hip.MaggieHipError('imd_prep: the ground-truth alphas must be an integer multiple of the OS8 map')
+    L = NF * h * w
+    feat_ids = torch.empty((B, L), dtype=torch.int32, device=mask.device)
+    valid_u8 = ACC((B * n_i + 3) // 4, mask.device).view(torch.uint8)                 # zeroed by the callee (or the graph's zero arena)
+    guidance = torch.empty((B, n_i, L), dtype=torch.float32, device=mask.device) if gt is not None else None
+    hip.call('mg_imd_prep', hip.ptr(mask), c_int(n_in), c_int(s), hip.ptr(gt), c_int(0 if gt is None else gt.shape[2]), c_int(gs), c_int(B), c_int(NF),
+             c_int(h), c_int(w), c_int(n_i), hip.ptr(feat_ids), hip.ptr(guidance), hip.ptr(valid_u8), hip.stream())
+    return feat_ids, guidance, valid_u8[:B * n_i].view(B, n_i)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # temporal (video) elementwise kernels: ConvGRU gate math, eval-time alpha aggregation
 # ------------------------------------------------------------------------------------------------------------------

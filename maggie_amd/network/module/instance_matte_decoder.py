@@ -80,20 +80,14 @@ class InstanceMatteDecoder(nn.Module):
             raise MF.K.hip.MaggieHipError('InstanceMatteDecoder: the guidance mask must be an integer multiple of the OS8 map (%dx%d), got %dx%d'
                                           % (h, w, mask.shape[-2], mask.shape[-1]))
         mk = mask.float().contiguous()
-        gm = gs = None
+        gm = None
         if self.training:
             gm = gt_mask.float().contiguous()
             gs = gm.shape[-1] // w
             if gs < 1 or gm.shape[-1] != w * gs or gm.shape[-2] != h * gs:
                 raise MF.K.hip.MaggieHipError('InstanceMatteDecoder: the ground-truth alphas must be an integer multiple of the OS8 map')
-        L = n_f * h * w
-        feat_ids = torch.empty((b, L), dtype=torch.int32, device=mask.device)
-        valid_u8 = MF.ARENA.acc((b * n_i + 3) // 4, mask.device).view(torch.uint8)               # zeroed by the callee (or the graph's zero arena)
-        guidance_mask = torch.empty((b, n_i, L), dtype=torch.float32, device=mask.device) if self.training else None
-        MF.K.hip.call('mg_imd_prep', MF.K.hip.ptr(mk), MF.K.c_int(n_in), MF.K.c_int(stride), MF.K.hip.ptr(gm), MF.K.c_int(0 if gm is None else gm.shape[2]),
-                      MF.K.c_int(gs or 1), MF.K.c_int(b), MF.K.c_int(n_f), MF.K.c_int(h), MF.K.c_int(w), MF.K.c_int(n_i), MF.K.hip.ptr(feat_ids),
-                      MF.K.hip.ptr(guidance_mask), MF.K.hip.ptr(valid_u8), MF.K.hip.stream())
-        token_padding_mask = valid_u8[:b * n_i].view(b, n_i) == 0
+        feat_ids, guidance_mask, valid_u8 = MF.K.imd_prep(mk, gm, h, w, n_i)
+        token_padding_mask = valid_u8 == 0
         id_table = self.id_embedding.weight.float() if self.use_id_pe else None
         # materialised once: every token-side launch below wants dense (b, 10, d) operands (an expanded view would be copied per use)
         token_pos = self.id_embedding.weight[1:self.max_inst + 1].float()[None].expand(b, -1, -1).contiguous()

@@ -744,6 +744,34 @@ int mg_photo_noise(const uint8_t* in, void* out, const uint8_t* lut, const int16
 int mg_jpeg_limits(int* tile_rows, int* tile_cols, int* threads, int* max_side);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * MotionBlur of the video training stream on the device (csrc/motion.hip; maggie/dataloader/transforms.py:965-1034, vim.py:52): the kernel
+ * albumentations draws is one 8-connected line of n <= 49 ones in a ksize x ksize box (ksize odd, 3..49) divided by n, so every plane is
+ *   out[y][x] = rhe( sum_k src[r101(y + dy_k, h)][r101(x + dx_k, w)] / n )
+ * with (dy_k, dx_k) the offsets of the line's pixels from the anchor ksize / 2 (correlation, no flip), r101 OpenCV's BORDER_REFLECT_101
+ * (0 for a length of 1; repeated for sources smaller than the reach) and rhe round-half-to-even of the exact rational: integer work only.
+ *   taps             : DEVICE int32 [MG_MOTION_TABLE]: [0] = n, [1] = ksize, then n (dy, dx) pairs in the kernel's row-major order. The launch
+ *                      geometry does not depend on it; the kernel clamps n to 1..MG_MOTION_MAX_TAPS and every offset to +-MG_MOTION_MAX_KSIZE / 2
+ *                      and reads 2 + 2 n entries, so a captured launch follows a table rewritten between replays and no table can send a read
+ *                      outside the LDS tile.
+ *   mg_motion_frames : in uint8 [frames][h][w][3] -> out uint8 in the same layout (MG_PHOTO_RAW) or fp32 [frames][3][h][w] =
+ *                      (v / 255 - mean[c]) / std[c] (MG_PHOTO_NORM), the bits of mg_preprocess_image on the raw result.
+ *   mg_motion_planes : uint8 [planes][h][w] in and out.
+ * A workgroup of MG_MOTION_THREADS lanes owns MG_MOTION_TILE_ROWS x MG_MOTION_TILE_COLS output pixels. Each returns -2 for an argument error
+ * (before any launch; h, w <= MG_MOTION_MAX_SIDE, in != out), -3 when the launch would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_MOTION_MAX_KSIZE 49
+#define MG_MOTION_MAX_TAPS 49
+#define MG_MOTION_TABLE (2 + 2 * MG_MOTION_MAX_TAPS)
+#define MG_MOTION_TILE_ROWS 32
+#define MG_MOTION_TILE_COLS 64
+#define MG_MOTION_THREADS 256
+#define MG_MOTION_MAX_SIDE 32767
+int mg_motion_frames(const uint8_t* in, void* out, const int32_t* taps, long frames, int h, int w, int epilogue, const float* mean3,
+                     const float* std3, void* stream);
+int mg_motion_planes(const uint8_t* in, uint8_t* out, const int32_t* taps, long planes, int h, int w, void* stream);
+int mg_motion_limits(int* max_ksize, int* max_taps, int* tile_rows, int* tile_cols, int* table_len, int* max_side);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

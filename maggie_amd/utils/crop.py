@@ -15,9 +15,9 @@ tables of the padding branch are `geometry.resize_tables` on the padded size (`m
 window written into `draws.window` between replays.
 
 What stays with the caller: the draws of GammaContrast, AdditiveGaussionNoise and JpegCompression (imgaug's own generators; no equality with
-them is claimed), which follow the flip in the reference's stream and precede the mask chain's, and MotionBlur for video. The steps
-themselves have device forms: `lut` here is a per-channel tone curve the caller drew, utils/photometric.py has the noise and the JPEG round
-trip, utils/affine.py RandomAffine with its draws. Also the caller's: the `> 127` area filter and the random instance removal of
+them is claimed), which follow the flip in the reference's stream and precede the mask chain's, and the kernel of MotionBlur for video. The
+steps themselves have device forms: `lut` here is a per-channel tone curve the caller drew, utils/motion.py has MotionBlur, utils/photometric.py
+the noise and the JPEG round trip, utils/affine.py RandomAffine with its draws. Also the caller's: the `> 127` area filter and the random instance removal of
 him.py:119-149.
 
 Wrong dtype, rank or size raise before a launch; a crop larger than the image raises the reference's ValueError. There is no CPU fallback."""

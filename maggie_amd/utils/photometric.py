@@ -20,7 +20,8 @@ no tolerance anywhere. A `PhotoDraws` moved to the device (`.to(device)`) makes 
 captured in a graph and new values written into `lut`, `noise` and `qtable` between replays.
 
 What stays with the caller: the draws themselves (imgaug's generators for the gamma, the noise sample and the compression; no equality with
-them is claimed), and MotionBlur of the video loader (vim.py:52), whose kernel albumentations draws with cv2.line. The alphas and masks are not
+them is claimed). MotionBlur of the video loader (vim.py:52), which runs between the tone curve and the noise, has its own module:
+utils/motion.py (`DevicePreprocessor.train_item_motion` puts the curve on the crop's table so that it precedes the blur). The alphas and masks are not
 touched (the reference's alpha line in JpegCompression is commented out). Wrong dtype, rank or size raise before a launch. There is no CPU
 fallback."""
 import numpy as np

@@ -15,6 +15,7 @@ import torch
 from .. import hip
 from ..hip import c_int, c_long
 from . import affine, crop, geometry, groundtruth, maskgen, photometric
+from . import motion as motion_blur                   # `motion` is the argument's name in the training item
 from ._inputs import IMAGENET_MEAN, IMAGENET_STD, check_u8, float3, resolve_device          # the two constants are this module's public names too
 
 
@@ -154,6 +155,29 @@ class DevicePreprocessor:
                                           mask_draws=mask_draws, lut=lut, warp_masks=warp_masks)
         return self._train_item(frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks)
 
+    def train_item_motion(self, frames_u8, alphas_u8, masks_u8, crop_draws, motion, photo=None, affine_draws=None, slot_ids=None, *,
+                          transition=None, mask_draws=None, lut=None, warp_masks=False):
+        """The video training item (vim.py:49-55): `train_item_photo` with MotionBlur (transforms.py:965-1034; utils/motion.py) between
+        GammaContrast and AdditiveGaussionNoise. `motion`: a motion_blur.MotionDraws (`motion.draw`), or None. None, or draws that did not
+        fire, give `train_item_photo` itself, bit for bit and as a call of it. Fired draws take the raw uint8 crop, on whose table every tone
+        curve rides (`lut`, then `photo.lut`: Gamma comes before the blur), and blur the frames and the alphas with the one kernel; noise / JPEG
+        and the affine follow as before, and Normalize belongs to the last stage that touches the frames -- the blur's epilogue when neither
+        follows. 'alpha', `transition` and the affine read the blurred alphas. The masks: with `masks_u8 is alphas_u8` or `warp_masks=True`
+        (the video loader regenerates them from the final alphas, vim.py:58-59) the mask chain reads the blurred (and, with `warp_masks`, warped)
+        alphas; separate masks are not blurred, as in the reference."""
+        self._check_draws(photo, affine_draws)
+        if motion is not None and not isinstance(motion, motion_blur.MotionDraws):
+            raise TypeError('motion must be a motion.MotionDraws or None (got %s)' % type(motion).__name__)
+        if motion is None or not motion.fired:
+            return self.train_item_photo(frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition=transition,
+                                         mask_draws=mask_draws, lut=lut, warp_masks=warp_masks)
+        if photo is not None:                                                                         # the tone curve precedes the blur
+            if photo.lut is not None:
+                lut = photo.lut if lut is None else photometric.compose_luts(lut, photo.lut, resolve_device(self.device, frames_u8))
+            photo = photometric.PhotoDraws(None, photo.noise, photo.quality, photo.qtable) if photo.fired else None
+        return self._train_item(frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks,
+                                motion)
+
     @staticmethod
     def _check_draws(photo, affine_draws):
         if photo is not None and not isinstance(photo, photometric.PhotoDraws):
@@ -161,28 +185,33 @@ class DevicePreprocessor:
         if affine_draws is not None and not isinstance(affine_draws, affine.AffineDraws):
             raise TypeError('affine_draws must be an affine.AffineDraws or None (got %s)' % type(affine_draws).__name__)
 
-    def _train_item(self, frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks):
-        """The one wiring of the training item, in the order of the reference's stream: crop -> (noise / JPEG) -> (RandomAffine) -> assemble.
-        `photo`: fired PhotoDraws or None (a lone tone curve has joined `lut` by now). Every routing decision is made here, once; DESIGN.md
-        section 20 has the table of which launch writes 'image'."""
+    def _train_item(self, frames_u8, alphas_u8, masks_u8, crop_draws, photo, affine_draws, slot_ids, transition, mask_draws, lut, warp_masks,
+                    motion=None):
+        """The one wiring of the training item, in the order of the reference's stream: crop -> (MotionBlur) -> (noise / JPEG) ->
+        (RandomAffine) -> assemble. `photo`: fired PhotoDraws or None (a lone tone curve has joined `lut` by now); `motion`: fired MotionDraws
+        or None (then `photo` carries no tone curve). Every routing decision is made here, once; DESIGN.md section 20 has the table of which
+        launch writes 'image'."""
         self._check_draws(photo, affine_draws)
         if len(frames_u8.shape) != 4:
             raise ValueError('frames must be (T, H, W, 3) (got shape %s)' % (tuple(frames_u8.shape),))
         warped = affine_draws is not None and affine_draws.fired
-        # the mask chain reads the warped alphas (the video loader's wiring), or the cropped alphas when the masks ARE the alphas, or the
-        # cropped masks; only the last makes the crop touch `masks_u8`
-        shared, from_warp = masks_u8 is alphas_u8, warped and warp_masks and masks_u8 is not None
-        # Normalize belongs to the last stage that touches the frames: the crop's epilogue, the photometric one, or affine.shift_normalize
-        f, a, m = crop.apply(frames_u8, alphas_u8, None if (shared or from_warp) else masks_u8, crop_draws, normalize=photo is None and not warped,
-                             lut=lut, mean=self.mean, std=self.std, device=self.device)
+        blurred = motion is not None
+        # the mask chain reads the final alphas (the video loader's wiring: blurred and / or warped), or the cropped (and blurred) alphas when the
+        # masks ARE the alphas, or the cropped masks; only the last makes the crop touch `masks_u8`
+        shared, from_alpha = masks_u8 is alphas_u8, (warped or blurred) and warp_masks and masks_u8 is not None
+        # Normalize belongs to the last stage that touches the frames: the crop's epilogue, the blur's, the photometric one, or affine.shift_normalize
+        f, a, m = crop.apply(frames_u8, alphas_u8, None if (shared or from_alpha) else masks_u8, crop_draws,
+                             normalize=photo is None and not warped and not blurred, lut=lut, mean=self.mean, std=self.std, device=self.device)
+        if blurred:                                                                                   # reads raw uint8; one kernel for frames and alphas
+            f, a = motion_blur.apply(f, a, motion, normalize=photo is None and not warped, mean=self.mean, std=self.std, device=self.device)
         if shared:
             m = a
         if photo is not None:
             f = photometric.apply(f, photo, normalize=not warped, mean=self.mean, std=self.std, device=self.device)
         if warped:                                                                                    # reads raw uint8
             f, a = affine.apply(f, a, affine_draws, self.mean, self.std, device=self.device)
-            if from_warp:
-                m = a
+        if from_alpha:
+            m = a
         return self._assemble(f, a, m, slot_ids, transition, False, mask_draws)
 
     def eval_item(self, frames_u8, ori_alphas_u8, masks_u8=None, *, short_size=768, divisor=64, trimap=True):

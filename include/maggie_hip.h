@@ -819,6 +819,30 @@ int mg_metric_conn(const float* pred, const float* gt, const float* trimap, int 
 int mg_postprocess_largest_cc(const float* alpha, int P, int H, int W, float thresh, void* scratch, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Dense Farneback optical flow and the MESSDdt metric (csrc/flow.hip; maggie/utils/metric.py:450-531). fp32 arithmetic; every scratch
+ * buffer comes from the caller; no host synchronisation and no allocation; the launch count depends on the pyramid depth only.
+ *   mg_flow_levels          : pyramid levels below full size for H x W planes (0..5): halve while both sides stay >= 32
+ *   mg_flow_farneback       : prev, next u8 [P][H][W] -> flow f32 [P][H][W][2] ([..][0] along columns, [..][1] along rows;
+ *                             next(p + flow) ~ prev(p)). The parameters are those of cv2.calcOpticalFlowFarneback and must be the
+ *                             reference's (0.5, 5, 10, 2, 7, 1.5, MG_FLOW_GAUSSIAN), else -2. scratch: mg_flow_scratch_bytes.
+ *   mg_metric_messddt       : pred / gt / trimap (may be NULL; mask = trimap == 1) f32 [F][N][H][W] -> out f64 [N][2] =
+ *                             { sum_t sum |error_map|, sum_t (sum m_t + 1) } with error_map = (p_t - g_t)^2 m_t - (p' - g')^2 m', the primed
+ *                             sample read as the reference reads it: for pixel (row i, column j) at row clamp(j + fx, 0, H-1), column
+ *                             clamp(i + fy, 0, W-1) of FRAME 1, for every t. The flow is that of the planes (uint8)(gt * 255.0f), rounded
+ *                             half to even; `flow_in` (f32 [F-1][N][H][W][2], tests) replaces it, `flow_out` receives it; both may be
+ *                             NULL. F < 2: zeros. scratch: mg_messddt_scratch_bytes.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_FLOW_GAUSSIAN 256       /* cv2.OPTFLOW_FARNEBACK_GAUSSIAN */
+#define MG_FLOW_MAX_SIDE 32767
+int mg_flow_levels(int H, int W);
+int mg_flow_scratch_bytes(long P, int H, int W, long* bytes);
+int mg_flow_farneback(const uint8_t* prev, const uint8_t* next, long P, int H, int W, double pyr_scale, int levels, int winsize,
+                      int iterations, int poly_n, double poly_sigma, int flags, void* scratch, float* flow, void* stream);
+int mg_messddt_scratch_bytes(int F, int N, int H, int W, long* bytes);
+int mg_metric_messddt(const float* pred, const float* gt, const float* trimap, int F, int N, int H, int W, const float* flow_in,
+                      void* scratch, float* flow_out, double* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Sparse refinement head with a DEVICE row count (round 2).
  * The reference's detail stage (maggie/network/decoder/resnet_inst_matt_spconv.py:196-270) sizes every spconv feature matrix from
  * `torch.nonzero` (:206) -- a device->host read per forward, after which ~430 small launches are paced by the host. Here the site

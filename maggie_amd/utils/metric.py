@@ -9,13 +9,16 @@ the planes (HIP kernels mg_metric_plane_sums / mg_metric_grad / mg_metric_dtssd)
 reference copies every plane to the host, reduces in numpy and, for Grad, ships the planes back to the GPU.
 Conn (:224-300; mg_metric_conn: the largest 4-connected component at each of the 10 threshold levels, csrc/ccl.hip) is built by
 build_metric(..., device_conn=True); by default it stays with the caller.
-MESSDdt (optical-flow warping on the CPU: cv2) stays with the caller, as SURVEY 8f says."""
+MESSDdt (:450-531; mg_metric_messddt: dense Farneback flow of the ground truth and the reference's flow-warped error, csrc/flow.hip) is built
+by build_metric(..., device_flow=True). Its flow restates the published algorithm at the reference's parameters and is not compared with
+cv2.calcOpticalFlowFarneback (cv2 is not part of this build); its warp and reduction are pinned to the reference's code."""
 import numpy as np
 import torch
 
 from .. import hip
 from ..hip import c_int, c_long
 from . import connected
+from . import flow as _flow
 
 
 def _planes(x):
@@ -144,13 +147,64 @@ class Conn(Metric):
         return float(out.sum()) * 0.001, P
 
 
+class MESSDdt(Metric):
+    """Flow-warped temporal error (metric.py:450-531). `pred`, `gt`, `trimap`: fp32 device tensors (F, N_i, H, W) (a leading 1 is squeezed,
+    :504-506); mask = (trimap == 1) or all ones. Per instance and frame pair t, with the Farneback flow of the ground truth planes
+    (uint8)(gt * 255.0f) rounded half to even:
+
+        error_map = (p_t - g_t)^2 m_t - (p' - g')^2 m',   e = sum_t sum |error_map| / sum_t (sum m_t + 1)
+
+    and the instance adds 10000 e to the score and 1 to the count. The primed planes are read exactly as metric.py:481-492 reads them, which
+    is not what a flow warp would be: for pixel (row i, column j) the sample sits at row clamp(j + fx, 0, H-1), column clamp(i + fy, 0, W-1)
+    -- the coordinates transposed, each clamped with the other axis's bound -- and `torch.take` on the flattened (F-1, H, W) tensor carries no
+    frame offset, so the sample always comes from FRAME 1, for every t. The published numbers were produced this way; it is reproduced, and
+    there is no "corrected" mode. F < 2 contributes nothing (the reference's `except: continue`). Only two doubles per instance are read back."""
+
+    def __init__(self):
+        super().__init__()
+        self.last_flow = None
+
+    def update(self, pred, gt, trimap=None, flow=None, keep_flow=False, **kargs):
+        """`flow` (tests): fp32 (F-1, N_i, H, W, 2) used instead of the computed one; `keep_flow`: leave the computed flow in `last_flow`."""
+        hip.need_cuda(pred, gt, trimap)
+        if pred.dim() == 5:
+            pred, gt = pred.squeeze(0), gt.squeeze(0)
+            trimap = None if trimap is None else trimap.squeeze(0)
+        if pred.dim() != 4 or pred.shape != gt.shape or (trimap is not None and trimap.shape != gt.shape):
+            raise hip.MaggieHipError('MESSDdt needs pred, gt and trimap of one shape (F, N_i, H, W) (got %s, %s)' % (tuple(pred.shape), tuple(gt.shape)))
+        F, N, H, W = pred.shape
+        if F < 2 or N == 0:
+            return 0.0
+        pred, gt = pred.float().contiguous(), gt.float().contiguous()
+        tri = None if trimap is None else trimap.float().contiguous()
+        if flow is not None:
+            hip.need_cuda(flow)
+            if tuple(flow.shape) != (F - 1, N, H, W, 2):
+                raise hip.MaggieHipError('MESSDdt: flow must be (F-1, N_i, H, W, 2) (got %s)' % (tuple(flow.shape),))
+            flow = flow.float().contiguous()
+        out = torch.empty((N, 2), dtype=torch.float64, device=pred.device)
+        ws = _flow.messddt_scratch(F, N, H, W, pred.device)
+        self.last_flow = torch.empty((F - 1, N, H, W, 2), dtype=torch.float32, device=pred.device) if keep_flow and flow is None else None
+        hip.call('mg_metric_messddt', hip.ptr(pred), hip.ptr(gt), hip.ptr(tri), c_int(F), c_int(N), c_int(H), c_int(W), hip.ptr(flow), hip.ptr(ws),
+                 hip.ptr(self.last_flow), hip.ptr(out), hip.stream())
+        error = float((out[:, 0] / out[:, 1]).sum()) * 10000
+        self.score += error
+        self.count += N
+        return error / (N + 1e-8)
+
+
 _DEVICE_METRICS = {'SAD': SAD, 'MSE': MSE, 'MAD': MAD, 'Grad': Grad, 'dtSSD': dtSSD}
 
 
-def build_metric(metrics, device_conn=False):
-    """{name: metric object} like metric.py:534-538, for the metrics that live on the device. 'Conn' is built on the device only with
-    device_conn=True; without it (and for 'MESSDdt' always) a host-side metric raises NotImplementedError."""
-    known = dict(_DEVICE_METRICS, Conn=Conn) if device_conn else _DEVICE_METRICS
+def build_metric(metrics, device_conn=False, device_flow=False):
+    """{name: metric object} like metric.py:534-538, for the metrics that live on the device. 'Conn' is built only with device_conn=True and
+    'MESSDdt' only with device_flow=True; without the flag a metric the caller keeps on the host raises NotImplementedError. With both flags
+    every metric of the reference is built here."""
+    known = dict(_DEVICE_METRICS)
+    if device_conn:
+        known['Conn'] = Conn
+    if device_flow:
+        known['MESSDdt'] = MESSDdt
     missing = [m for m in metrics if m not in known]
     if missing:
         raise NotImplementedError('host-side metrics (skimage / cv2) are not part of this build: %s' % missing)

@@ -772,6 +772,56 @@ int mg_motion_planes(const uint8_t* in, uint8_t* out, const int32_t* taps, long 
 int mg_motion_limits(int* max_ksize, int* max_taps, int* tile_rows, int* tile_cols, int* table_len, int* max_side);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Compositing (csrc/compose.hip): Pillow's Image.resize / Image.paste and the occlusion bookkeeping of tools/synthesize_image_him.py and
+ * tools/synthesize_video_him.py on uint8 data, exact. `ps` = bytes per pixel: 1 (planes) or 3 (interleaved frames).
+ *   mg_compose_resize    : src uint8 [n][src_h][src_w][ps], the crop (cx, cy, cw, ch) of every image -> out uint8 [n][out_h][out_w][ps]. xtab / ytab:
+ *                          DEVICE int32 [out_w][MG_COMPOSE_TAB_HEADER + kx] / [out_h][.. + ky], a row = (first source index, tap count, 0, 0, taps in
+ *                          2^-22 units, zeros up to kx); kx, ky multiples of 4, tables 16-byte aligned. NULL = that pass is a copy (its size must
+ *                          not change). Pass: clip8((2^21 + sum in * tap) >> 22), horizontal first, a byte between the passes. regime
+ *                          MG_COMPOSE_FUSED: one launch, the horizontal results of a tile's source rows as bytes in LDS (the host promises at most
+ *                          MG_COMPOSE_MAX_ROWS rows per MG_COMPOSE_TILE_ROWS output rows; the kernel clamps); MG_COMPOSE_TWO_PASS: two launches
+ *                          through tmp (n * ch rows of out_w * ps rounded up to 16 bytes, 16-byte aligned; unused without ytab). Same bytes. Every
+ *                          table entry is clamped to the source, so a captured launch follows tables rewritten between replays.
+ *   mg_compose_paste     : dst [dst_h][dst_w][ps] <- src [src_h][src_w][ps] at (x, y), clipped to dst; mask [src_h][src_w] or NULL (a copy):
+ *                          t = dst (255 - m) + src m + 128, ((t >> 8) + t) >> 8.
+ *   mg_compose_try_place : planes [>= n_prev][h][w] of fp32 / fp64 (dtype), a uint8 [ha][wa] placed at (x, y) (clipped), lut [256] = v / 255 in the
+ *                          planes' type. Writes nothing but out, DEVICE fp64 [2 MG_COMPOSE_MAX_PLANES + 1]: [j] = sum plane_j (1 - a / 255),
+ *                          [MAX_PLANES + j] = sum plane_j for j < n_prev, [2 MAX_PLANES] = sum a / 255, zeros elsewhere; the product and 1 - x in
+ *                          the planes' type, the sums in fp64: MG_COMPOSE_SUM_BLOCKS partials per sum in `partial` (fp64
+ *                          [2 MAX_PLANES + 2][SUM_BLOCKS]), each a fixed tree over a strided chunk, added in index order. No atomics.
+ *   mg_compose_commit    : one launch: image [h][w][3] masked paste of fg [ha][wa][3] through a; canvas [h][w][3] = fg inside the box, 0 outside;
+ *                          plane idx = a / 255 inside, 0 outside; planes j < idx *= 1 - a / 255. image, canvas (and fg with both) may be NULL.
+ *   mg_compose_planes_u8 : out = trunc(plane * 255) (product in the planes' type), flags int32 [count] = 1 where a plane holds a non-zero value.
+ *   mg_compose_alpha_box : box int32 [4] = min x, min y, max x, max y of alpha > 0 (w, h, -1, -1 for an all-zero plane).
+ * Each returns -2 for an argument error before any launch (sides 1..MG_COMPOSE_MAX_SIDE), -3 when a launch would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_COMPOSE_TILE_ROWS 16
+#define MG_COMPOSE_TILE_BYTES 192
+#define MG_COMPOSE_MAX_ROWS 128
+#define MG_COMPOSE_LDS_BYTES (MG_COMPOSE_MAX_ROWS * MG_COMPOSE_TILE_BYTES)
+#define MG_COMPOSE_THREADS 256
+#define MG_COMPOSE_TAB_HEADER 4
+#define MG_COMPOSE_MAX_PLANES 10
+#define MG_COMPOSE_SUM_BLOCKS 64
+#define MG_COMPOSE_MAX_SIDE 32767
+#define MG_COMPOSE_FUSED 0
+#define MG_COMPOSE_TWO_PASS 1
+#define MG_COMPOSE_F32 0
+#define MG_COMPOSE_F64 1
+int mg_compose_resize(const uint8_t* src, uint8_t* out, uint8_t* tmp, const int32_t* xtab, const int32_t* ytab, long n, int ps, int src_h,
+                      int src_w, int cx, int cy, int cw, int ch, int out_h, int out_w, int kx, int ky, int regime, void* stream);
+int mg_compose_paste(uint8_t* dst, const uint8_t* src, const uint8_t* mask, int ps, int dst_h, int dst_w, int src_h, int src_w, int x, int y,
+                     void* stream);
+int mg_compose_try_place(const void* planes, const uint8_t* a, const void* lut, double* partial, double* out, int dtype, int h, int w, int ha,
+                         int wa, int x, int y, int n_prev, void* stream);
+int mg_compose_commit(uint8_t* image, uint8_t* canvas, void* planes, const uint8_t* fg, const uint8_t* a, const void* lut, int dtype, int h, int w,
+                      int ha, int wa, int x, int y, int idx, void* stream);
+int mg_compose_planes_u8(const void* planes, uint8_t* out, int32_t* flags, int dtype, long count, int h, int w, void* stream);
+int mg_compose_alpha_box(const uint8_t* alpha, int32_t* box, int h, int w, void* stream);
+int mg_compose_limits(int* tile_rows, int* tile_bytes, int* max_rows, int* lds_bytes, int* tab_header, int* max_planes, int* sum_blocks,
+                      int* max_side);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Validation metrics on the device (maggie/utils/metric.py). fp32 planes, fp64 results. `trimap` may be NULL;
  * mask_mode: 0 = all ones, 1 = (trimap > 0) (Metric.update :47), 2 = (trimap == 1) (dtSSD.update :427).
  *   mg_metric_plane_sums: out[P][3] = per plane { sum |pred-gt| m, sum (pred-gt)^2 m, sum m }      (SAD :68-78, MSE :80-90, MAD :92-97)

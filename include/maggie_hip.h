@@ -1076,6 +1076,57 @@ int mg_mailbox_bn_finalize_dev(const mg_mailbox* mb, const float* stats, int nre
                                const float* beta, float* running_mean, float* running_var, float momentum, float eps, float* outs, float* count_out,
                                uint32_t* seq_dev, int32_t* err_dev, long spin_ticks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Baseline JPEG decoding (csrc/jpegdec.hip): the entropy-coded segments of `frames` files of one geometry -> RGB on the device. Replaces T.Load
+ * (maggie/dataloader/transforms.py:38-66: Image.open(path).convert("RGB")) for SOF0 files with one interleaved scan, 4:2:0, 4:4:4 or greyscale.
+ * The Huffman decoding is the self-synchronising parallel form: the segment is cut into subsequences of `sub_bytes` raw
+ * bytes, one lane each.
+ *   tabs    : int32 [frames][MG_JPEGDEC_TAB_WORDS], one record per frame: four Huffman tables (DC 0, DC 1, AC 0, AC 1) of 228 words each
+ *             (look uint16[256] = len << 8 | symbol for codes of at most 8 bits, else 0; maxcode int32[18] by length, -1 = none; valoff int32[18]
+ *             = index of the length's first value minus its first code; vals uint8[256]); words 912..917 the block slots of an MCU
+ *             (DC table | AC table << 4); 918 the segment's offset in `data`, 919 its length, 920 the restart interval in MCUs (0 = none);
+ *             928..1119 the quantisation tables of components 0, 1, 2 in natural order.
+ *   mg_jpegdec_sync  : launch number `launch` (0, 1, 2, ...) of the synchronisation. exits uint64 [frames][nsub] (a subsequence's exit state:
+ *             raw bit position | slot << 40 | zig-zag index << 44), counts int32 [frames][nsub] (blocks completed), entries uint64
+ *             [frames][ceil(nsub / MG_JPEGDEC_THREADS)], bounds uint64 [2][frames][ceil(nsub / MG_JPEGDEC_THREADS)]; info int32 [info_words],
+ *             zeroed by the caller: [0] status bits, [2 + 2 k] nonzero when launch k moved a workgroup's exit state (another launch is needed),
+ *             [3 + 2 k] the rounds launch k ran inside a workgroup. nsub = ceil(longest segment / sub_bytes).
+ *   mg_jpegdec_coef  : counts -> first_block int32 [frames][nsub] (exclusive sum), then coef int16 [frames][blocks][64] (zero-filled by the
+ *             caller; scan order, natural order inside a block, the DC term as its difference) and the status bits.
+ *   mg_jpegdec_dcsum : DC differences -> DC terms, per component within each restart interval.
+ *   mg_jpegdec_idct  : coef x table -> inverse DCT -> planes uint8: 4:2:0 in mg_jpeg_rgb's layout (finish with mg_jpeg_rgb); 4:4:4 Y, Cb, Cr
+ *             [frames][h8][w8] each; greyscale Y [frames][h8][w8] (h8, w8 = h, w rounded up to 8).
+ *   mg_jpegdec_rgb   : the 4:4:4 / greyscale planes -> out, the epilogues of mg_jpeg_rgb.
+ * Each returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension. Sizes (`data_bytes`,
+ * `coef_elems`, `plane_bytes`) are checked against the geometry and bound every access.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_JPEGDEC_420 0
+#define MG_JPEGDEC_444 1
+#define MG_JPEGDEC_GREY 2
+#define MG_JPEGDEC_THREADS 128
+#define MG_JPEGDEC_TAB_WORDS 1120
+#define MG_JPEGDEC_MIN_SUB 8 /* 16 code bits + 11 value bits = 4 data bytes, each of which may drag a stuffed byte */
+#define MG_JPEGDEC_MAX_SUB 4096
+#define MG_JPEGDEC_DEFAULT_SUB 8 /* the best of tools/jpegdec_bench.py's sweep on its 1080 x 1920 file */
+#define MG_JPEGDEC_MAX_BYTES (1L << 28)
+#define MG_JPEGDEC_ST_INDEX 1    /* a zig-zag index past 63 */
+#define MG_JPEGDEC_ST_CODE 2     /* an unassigned code or a category above 11 */
+#define MG_JPEGDEC_ST_PAST_END 4 /* the segment ended before the last block */
+#define MG_JPEGDEC_ST_COUNT 8    /* the blocks decoded are not MCUs x blocks per MCU */
+#define MG_JPEGDEC_ST_RESTART 16 /* a restart marker off an interval's end, out of order, or without DRI */
+int mg_jpegdec_limits(int* threads, int* min_sub, int* max_sub, int* default_sub, int* tab_words);
+int mg_jpegdec_sync(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts,
+                    unsigned long long* entries, unsigned long long* bounds, int32_t* info, int info_words, long frames, int nsub, int sub_bytes,
+                    int layout, int launch, void* stream);
+int mg_jpegdec_coef(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
+                    int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h, int w, int layout,
+                    void* stream);
+int mg_jpegdec_dcsum(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int layout, void* stream);
+int mg_jpegdec_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h, int w, int layout,
+                    void* stream);
+int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int layout, int epilogue, const float* mean3,
+                   const float* std3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,394 @@
+"""Baseline JPEG files decoded on the device (HIP kernels of csrc/jpegdec.hip) -- the step in front of every input stage, the reference's
+`T.Load` (maggie/dataloader/transforms.py:38-66): `Image.open(path).convert("RGB")` of a `.jpg`. The loader reads the file's bytes; the
+pixels never exist on the host.
+
+  * `parse`        the marker walk, host only: size, sampling layout, quantisation and Huffman tables, restart interval, where the
+                   entropy-coded segment lies. Raises `Unsupported` (a ValueError) for everything outside the supported set, before any launch,
+                   so that a loader can fall back to PIL: `SOF0`, 8 bits, one interleaved scan, YCbCr 4:2:0 or 4:4:4 or one greyscale component.
+  * `decode`       one file -> uint8 (h, w, 3) on the device, or with `normalize` fp32 (3, h, w) with the bits of `normalize_frames`.
+  * `decode_clip`  T files of one geometry and layout (a video clip) -> (T, h, w, 3) or (T, 3, h, w) from ONE set of launches; tables and
+                   stream offsets are per frame.
+
+The Huffman decoding is the self-synchronising parallel form of Weissenberger and Schmidt: the segment is
+cut into subsequences of `sub_bytes` raw bytes, one lane each; launch 0 decodes every subsequence from its own first bit and settles each
+workgroup, every further launch carries exit states across workgroups, until a launch moves none. The number of rounds is at most the number
+of subsequences, and the launches at most the workgroups plus one; both bounds are computed here and a stream that exceeds them raises.
+Everything behind the coefficients is section 19's arithmetic (4:2:0 finishes through the existing `mg_jpeg_rgb`): equal to Pillow byte for byte.
+
+Decoding is data-dependent, so it is NOT graph-capturable: the host has to see whether the synchronisation settled. Read-backs per call:
+ONE in the usual case -- the output pass is launched behind the second synchronisation launch without waiting, and the `info` words (status,
+per-launch "moved" flags, rounds) come back once at the end. Only when that second launch still moved a workgroup's exit state (a stream
+that does not self-synchronise within a workgroup, such as a periodic one) is there one more read-back per further launch, and the output
+pass runs again. A status bit becomes a ValueError; libjpeg's warn-and-continue on corrupt files is not reproduced. Wrong types raise before
+any launch. There is no CPU fallback."""
+import numpy as np
+import torch
+
+from .. import hip
+from ..hip import c_int, c_long
+from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, integer, resolve_device
+from .photometric import MAX_SIDE, NORM, RAW, plane_bytes
+
+L420, L444, GREY = 0, 1, 2                                  # MG_JPEGDEC_420 / _444 / _GREY (include/maggie_hip.h)
+THREADS, TAB_WORDS, MIN_SUB, MAX_SUB, DEFAULT_SUB = 128, 1120, 8, 4096, 8        # MG_JPEGDEC_THREADS / _TAB_WORDS / _MIN_SUB / _MAX_SUB / _DEFAULT_SUB
+MAX_BYTES = 1 << 28                                         # MG_JPEGDEC_MAX_BYTES
+STATUS = {1: 'a zig-zag index past 63', 2: 'an unassigned Huffman code', 4: 'the entropy-coded segment ends before the last block',
+          8: 'the number of blocks is not MCUs x blocks per MCU', 16: 'a restart marker out of place'}
+BLOCKS_PER_MCU = {L420: 6, L444: 3, GREY: 1}
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+
+
+class Unsupported(ValueError):
+    """A JPEG file outside the set the device decodes (or not a JPEG file): fall back to PIL."""
+
+
+class JpegPlan:
+    """What `parse` found: `width`, `height`, `layout` (L420, L444 or GREY), `sampling` ((h, v) per component), `quantization` ({id: int32 (64,)
+    natural order}), `qtables` (int32 (3, 64): the table of each output component), `dc` / `ac` ({id: (counts uint8 (16,), values uint8 (n,))}),
+    `selectors` ((dc id, ac id) per component), `restart_interval` (MCUs, 0 = none), `offset` / `length` of the entropy-coded segment."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    @property
+    def geometry(self):
+        return self.height, self.width, self.layout
+
+    @property
+    def mcus(self):
+        side = 16 if self.layout == L420 else 8
+        return ((self.width + side - 1) // side) * ((self.height + side - 1) // side)
+
+
+def parse(data):
+    """The marker walk of one file's bytes -> JpegPlan. Host only; raises `Unsupported` by name for what the device does not decode."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
+    d = bytes(data)
+    n = len(d)
+    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
+        raise Unsupported('not a JPEG file (no SOI marker)')
+    quant, dc, ac = {}, {}, {}
+    frame = scan = None
+    ri = 0
+    p = 2
+    while True:
+        if p + 4 > n:
+            raise Unsupported('the file ends inside its headers')
+        if d[p] != 0xFF:
+            raise Unsupported('expected a marker at byte %d' % p)
+        m = d[p + 1]
+        if m == 0xFF:                                          # fill byte
+            p += 1
+            continue
+        if m == 0xD9:
+            raise Unsupported('EOI before any scan')
+        size = (d[p + 2] << 8) | d[p + 3]
+        seg = d[p + 4:p + 2 + size]
+        if size < 2 or p + 2 + size > n:
+            raise Unsupported('a marker segment runs past the end of the file')
+        if m == 0xC0:
+            if frame is not None:
+                raise Unsupported('more than one frame header')
+            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise Unsupported('a malformed SOF0 segment')
+            if seg[0] != 8:
+                raise Unsupported('%d-bit samples (only 8-bit baseline is decoded)' % seg[0])
+            frame = dict(height=(seg[1] << 8) | seg[2], width=(seg[3] << 8) | seg[4],
+                         comps=[(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(seg[5])])
+        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            names = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless', 0xC9: 'arithmetic-coded sequential',
+                     0xCA: 'arithmetic-coded progressive'}
+            raise Unsupported('SOF%d (%s): only SOF0 baseline is decoded' % (m - 0xC0, names.get(m, 'differential or arithmetic')))
+        elif m == 0xCC:
+            raise Unsupported('arithmetic coding conditioning (DAC)')
+        elif m == 0xC4:
+            q = 0
+            while q < len(seg):
+                if q + 17 > len(seg):
+                    raise Unsupported('a malformed DHT segment')
+                tc, th = seg[q] >> 4, seg[q] & 15
+                counts = np.frombuffer(seg[q + 1:q + 17], np.uint8)
+                total = int(counts.sum())
+                if tc > 1 or th > 1 or total > 256 or q + 17 + total > len(seg):
+                    raise Unsupported('a malformed DHT segment (class %d, id %d)' % (tc, th))
+                code = 0
+                for l in range(16):
+                    code += int(counts[l])
+                    if code > (2 << l):
+                        raise Unsupported('a DHT table whose code lengths overflow')
+                    code <<= 1
+                (ac if tc else dc)[th] = (counts.copy(), np.frombuffer(seg[q + 17:q + 17 + total], np.uint8).copy())
+                q += 17 + total
+        elif m == 0xDB:
+            q = 0
+            while q < len(seg):
+                if seg[q] >> 4:
+                    raise Unsupported('a 16-bit quantisation table')
+                if (seg[q] & 15) > 3 or q + 65 > len(seg):
+                    raise Unsupported('a malformed DQT segment')
+                t = np.zeros(64, np.int32)
+                t[ZIGZAG] = np.frombuffer(seg[q + 1:q + 65], np.uint8)
+                quant[seg[q] & 15] = t
+                q += 65
+        elif m == 0xDD:
+            if len(seg) != 2:
+                raise Unsupported('a malformed DRI segment')
+            ri = (seg[0] << 8) | seg[1]
+        elif m == 0xDC:
+            raise Unsupported('DNL (the height is defined after the scan)')
+        elif m == 0xEE and seg[:5] == b'Adobe' and len(seg) >= 12:
+            if seg[11] != 1:
+                raise Unsupported('an Adobe APP14 marker with transform %d (only YCbCr is decoded)' % seg[11])
+        elif m == 0xDA:
+            if frame is None:
+                raise Unsupported('SOS before SOF0')
+            ns = seg[0] if seg else 0
+            if len(seg) != 4 + 2 * ns:
+                raise Unsupported('a malformed SOS segment')
+            scan = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
+            p += 2 + size
+            break
+        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
+            raise Unsupported('marker 0xFF%02X is not decoded' % m)
+        p += 2 + size
+    comps = frame['comps']
+    if len(comps) not in (1, 3):
+        raise Unsupported('%d components (only YCbCr and greyscale are decoded)' % len(comps))
+    w, h = frame['width'], frame['height']
+    if h == 0:
+        raise Unsupported('DNL (the height is defined after the scan)')
+    if w < 1 or w > MAX_SIDE or h > MAX_SIDE:
+        raise Unsupported('%d x %d: sides of 1..%d are decoded' % (w, h, MAX_SIDE))
+    if [c[0] for c in comps] != [s[0] for s in scan]:
+        raise Unsupported('several scans, or a scan that does not hold every component in frame order')
+    sampling = tuple((c[1], c[2]) for c in comps)
+    if len(comps) == 1:
+        layout = GREY
+    elif sampling == ((2, 2), (1, 1), (1, 1)):
+        layout = L420
+    elif sampling == ((1, 1), (1, 1), (1, 1)):
+        layout = L444
+    else:
+        raise Unsupported('sampling %s (only 4:2:0 and 4:4:4 are decoded)' % (sampling,))
+    for c in comps:
+        if c[3] not in quant:
+            raise Unsupported('quantisation table %d is not defined' % c[3])
+    for _, td, ta in scan:
+        if td > 1 or ta > 1 or td not in dc or ta not in ac:
+            raise Unsupported('a scan that selects a Huffman table that is not defined (DC %d, AC %d)' % (td, ta))
+    # the entropy-coded segment: up to the first marker that is neither a stuffed 0xFF00 nor RSTn
+    start = p
+    while True:
+        p = d.find(b'\xff', p)
+        if p < 0 or p + 1 >= n:
+            raise Unsupported('no EOI marker behind the scan')
+        if d[p + 1] == 0 or 0xD0 <= d[p + 1] <= 0xD7:
+            p += 2
+            continue
+        if d[p + 1] == 0xFF:
+            p += 1
+            continue
+        break
+    if d[p + 1] == 0xDC:
+        raise Unsupported('DNL (the height is defined after the scan)')
+    if d[p + 1] != 0xD9:
+        raise Unsupported('several scans (marker 0xFF%02X behind the first)' % d[p + 1])
+    if p - start > MAX_BYTES - MAX_SUB:
+        raise Unsupported('an entropy-coded segment of %d bytes' % (p - start))
+    qt = np.stack([quant[comps[min(k, len(comps) - 1)][3]] for k in range(3)]).astype(np.int32)
+    return JpegPlan(width=w, height=h, layout=layout, sampling=sampling, quantization=quant, qtables=qt, dc=dc, ac=ac,
+                    selectors=tuple((s[1], s[2]) for s in scan), restart_interval=ri, offset=start, length=p - start)
+
+
+_WORDS = {}                                                 # huffman_words by table: a loader's files share a handful of tables
+
+
+def huffman_words(counts, values):
+    """`_huffman_words`, remembered per table (the Annex K tables recur in every file an encoder writes without optimising)."""
+    key = (bytes(counts), bytes(values))
+    if key not in _WORDS:
+        if len(_WORDS) >= 256:
+            _WORDS.clear()
+        _WORDS[key] = _huffman_words(counts, values)
+    return _WORDS[key]
+
+
+def _huffman_words(counts, values):
+    """One table as the 228 int32 words the kernels read: look uint16[256] (len << 8 | symbol for codes of at most 8 bits), maxcode[18]
+    (-1 = no code of that length), valoff[18] (index of the length's first value minus its first code), vals uint8[256]."""
+    look = np.zeros(256, np.uint16)
+    maxcode = np.full(18, -1, np.int32)
+    valoff = np.zeros(18, np.int32)
+    vals = np.zeros(256, np.uint8)
+    vals[:len(values)] = values
+    code = k = 0
+    for l in range(1, 17):
+        c = int(counts[l - 1])
+        if c:
+            valoff[l] = k - code
+            if l <= 8:
+                for i in range(c):
+                    look[(code + i) << (8 - l):(code + i + 1) << (8 - l)] = (l << 8) | int(values[k + i])
+            code += c
+            k += c
+            maxcode[l] = code - 1
+        code <<= 1
+    return np.concatenate([look.view(np.int32), maxcode, valoff, vals.view(np.int32)])
+
+
+def record(plan, offset):
+    """A frame's int32 record (MG_JPEGDEC_TAB_WORDS words, include/maggie_hip.h) with its segment at `offset + plan.offset` of the buffer."""
+    rec = np.zeros(TAB_WORDS, np.int32)
+    empty = (np.zeros(16, np.uint8), np.zeros(0, np.uint8))
+    for k, t in enumerate((plan.dc.get(0, empty), plan.dc.get(1, empty), plan.ac.get(0, empty), plan.ac.get(1, empty))):
+        rec[228 * k:228 * (k + 1)] = huffman_words(*t)
+    sel = plan.selectors
+    slots = [sel[0]] * 4 + [sel[1], sel[2]] if plan.layout == L420 else list(sel)
+    for s, (td, ta) in enumerate(slots):
+        rec[912 + s] = td | (ta << 4)
+    rec[918], rec[919], rec[920] = offset + plan.offset, plan.length, plan.restart_interval
+    rec[928:1120] = plan.qtables.reshape(-1)
+    return rec
+
+
+def _sub_bytes(sub_bytes):
+    s = DEFAULT_SUB if sub_bytes is None else integer(sub_bytes, 'sub_bytes')
+    if not MIN_SUB <= s <= MAX_SUB:
+        raise ValueError('sub_bytes must be in %d..%d (got %d)' % (MIN_SUB, MAX_SUB, s))
+    return s
+
+
+def planes_size(n, h, w, layout):
+    """The bytes of the component planes between mg_jpegdec_idct and the colour kernel."""
+    if layout == L420:
+        return plane_bytes(n, h, w)
+    return n * ((h + 7) // 8 * 8) * ((w + 7) // 8 * 8) * (1 if layout == GREY else 3)
+
+
+class Decoded:
+    """What `run` leaves on the device: `out`, the coefficient blocks `coef` (T, blocks, 64) int16 in scan order, the component `planes`, and
+    on the host `rounds` (rounds inside workgroups, summed over the launches), `launches`, `subsequences` (the bound of the rounds) and
+    `readbacks`."""
+
+
+def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+    """The launches themselves: `blob` uint8 device tensor holding the T segments, `recs` int32 (T, TAB_WORDS) host records whose offsets point
+    into it. `out`: a preallocated contiguous destination of the right size and dtype (else allocated). Returns a `Decoded`."""
+    S = _sub_bytes(sub_bytes)
+    recs = np.ascontiguousarray(recs, np.int32).reshape(-1, TAB_WORDS)
+    T = recs.shape[0]
+    dev = blob.device
+    hip.need_cuda(blob)
+    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+        raise TypeError('blob must be a contiguous 1-D uint8 tensor')
+    if T < 1 or (recs[:, 918] < 0).any() or (recs[:, 919] < 0).any() or int((recs[:, 918].astype(np.int64) + recs[:, 919]).max()) > blob.numel():
+        raise ValueError('a segment lies outside the buffer')
+    nsub = max(1, -(-int(recs[:, 919].max()) // S))
+    wgs = -(-nsub // THREADS)
+    max_launches = wgs + 1
+    epilogue = NORM if normalize else RAW
+    tabs = torch.from_numpy(recs).to(dev, non_blocking=True)
+    exits = torch.empty((T, nsub), dtype=torch.int64, device=dev)
+    counts = torch.empty((T, nsub), dtype=torch.int32, device=dev)
+    first = torch.empty((T, nsub), dtype=torch.int32, device=dev)
+    entries = torch.empty((T, wgs), dtype=torch.int64, device=dev)
+    bounds = torch.zeros((2, T, wgs), dtype=torch.int64, device=dev)
+    info = torch.zeros((4 + 2 * (max_launches + 1),), dtype=torch.int32, device=dev)
+    nblocks = ((w + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * \
+        ((h + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * BLOCKS_PER_MCU[layout]
+    coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
+    planes = torch.empty((planes_size(T, h, w, layout),), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
+    elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous %s tensor of %d elements on %s' % ('float32' if normalize else 'uint8', T * h * w * 3, dev))
+    st = hip.stream
+
+    def sync(k):
+        hip.call('mg_jpegdec_sync', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(entries),
+                 hip.ptr(bounds), hip.ptr(info), c_int(info.numel()), c_long(T), c_int(nsub), c_int(S), c_int(layout), c_int(k), st())
+
+    def output():
+        hip.call('mg_jpegdec_coef', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(first),
+                 hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(nsub), c_int(S), c_int(h), c_int(w), c_int(layout), st())
+        hip.call('mg_jpegdec_dcsum', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), c_long(T), c_int(h), c_int(w), c_int(layout), st())
+        hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
+                 c_int(h), c_int(w), c_int(layout), st())
+        if layout == L420:
+            hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
+        else:
+            hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),
+                     c_int(epilogue), float3(mean), float3(std), st())
+
+    sync(0)
+    k = 0
+    if wgs > 1:
+        k = 1
+        sync(1)
+    output()
+    host = info.cpu().numpy()
+    readbacks = 1
+    again = False
+    while k >= 1 and host[2 + 2 * k] != 0:
+        if k >= max_launches:
+            raise ValueError('the stream did not synchronise within %d launches' % (max_launches + 1))
+        k += 1
+        sync(k)
+        host = info.cpu().numpy()
+        readbacks += 1
+        again = True
+    if again:
+        coef.zero_()
+        info[0:1].zero_()
+        output()
+        host = info.cpu().numpy()
+        readbacks += 1
+    if host[0]:
+        raise ValueError('a corrupt entropy-coded segment: ' + '; '.join(v for b, v in STATUS.items() if host[0] & b))
+    r = Decoded()
+    r.out, r.coef, r.planes = out.reshape((T, 3, h, w) if normalize else (T, h, w, 3)), coef, planes
+    r.rounds, r.launches, r.subsequences, r.readbacks = int(host[3::2].sum()), k + 1, nsub, readbacks
+    return r
+
+
+def _clip(datas, normalize, mean, std, device, sub_bytes):
+    if isinstance(datas, (bytes, bytearray, memoryview)) or not hasattr(datas, '__len__'):
+        raise TypeError('datas must be a sequence of the bytes of JPEG files (got %s)' % type(datas).__name__)
+    if len(datas) < 1:
+        raise ValueError('datas must hold at least one file')
+    _sub_bytes(sub_bytes)
+    float3(mean), float3(std)
+    plans = [parse(d) for d in datas]
+    if any(p.geometry != plans[0].geometry for p in plans):
+        raise ValueError('the files of a clip must share one size and one sampling layout (got %s)' % sorted({p.geometry for p in plans}))
+    offsets = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
+    if offsets[-1] > MAX_BYTES:
+        raise Unsupported('%d bytes of files in one clip' % offsets[-1])
+    recs = np.stack([record(p, int(o)) for p, o in zip(plans, offsets[:-1])])
+    device = resolve_device(device)
+    blob = torch.frombuffer(bytearray(b''.join(bytes(d) for d in datas)), dtype=torch.uint8).to(device, non_blocking=True)
+    h, w, layout = plans[0].geometry
+    return run(blob, recs, h, w, layout, sub_bytes=sub_bytes, normalize=normalize, mean=mean, std=std)
+
+
+def decode_clip(datas, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, sub_bytes=None):
+    """T JPEG files (a sequence of bytes objects) of one size and one sampling layout -> uint8 (T, h, w, 3) on the device, or with `normalize`
+    fp32 (T, 3, h, w), from one set of launches. Files of differing geometry raise ValueError, unsupported ones `Unsupported`, corrupt entropy
+    coding ValueError. Not graph-capturable (the module docstring says why); one read-back in the usual case."""
+    return _clip(datas, normalize, mean, std, device, sub_bytes).out
+
+
+def decode(data, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, sub_bytes=None):
+    """The bytes of one JPEG file -> uint8 (h, w, 3) on the device: `np.asarray(Image.open(BytesIO(data)).convert("RGB"))`. With `normalize`
+    fp32 (3, h, w): ToTensor + Normalize of that, the bits of `normalize_frames`. `sub_bytes`: the subsequence length (None = the measured
+    default). Not graph-capturable: decoding is data-dependent and the host reads the `info` words back: one read-back in the usual case."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
+    return _clip([data], normalize, mean, std, device, sub_bytes).out[0]
+
+
+def decode_stats(datas, *, device=None, sub_bytes=None):
+    """`decode_clip` returning the whole `Decoded` record (coefficients, planes, rounds, launches, read-backs): for tests and tools/jpegdec_bench.py."""
+    return _clip(datas, False, IMAGENET_MEAN, IMAGENET_STD, device, sub_bytes)

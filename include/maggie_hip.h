@@ -1127,6 +1127,48 @@ int mg_jpegdec_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, u
 int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int layout, int epilogue, const float* mean3,
                    const float* std3, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * PNG decoding (csrc/pngdec.hip): the zlib streams (concatenated IDAT payloads) of `planes` non-interlaced files of one size -> the L plane of
+ * Image.open(path).convert("L") on the device. Replaces the alpha / mask half of T.Load (maggie/dataloader/transforms.py:47-50). DESIGN.md
+ * section 26. Colour type 0 and 3 at depth 1, 2, 4, 8; colour type 2, 4, 6 at depth 8.
+ *   recs    : int32 [planes][MG_PNGDEC_REC_WORDS], one record per file: [0] the offset of its zlib stream in `data`, [1] the stream's length
+ *             (the two header bytes and the Adler-32 trailer included), [2] colour type, [3] bit depth, [4] the number of palette entries
+ *             (256 for grey), [8..71] the 256-entry L table as bytes (grey: sample * 255 / (2^depth - 1); palette: L of each PLTE entry).
+ *   raw     : uint8 [planes][raw_stride], the inflated bytes h x (1 + rowbytes) of each file at the start of its slice; raw_stride a multiple
+ *             of 16 that holds the largest of them, `raw` 16-byte aligned, `data` 4-byte aligned.
+ *   info    : int32 [planes][MG_PNGDEC_INFO_WORDS], zeroed by the caller: [0] status bits (both kernels), [1] rounds, [2] deflate blocks,
+ *             [3] tokens, [4] the Adler-32 computed, [5] the Adler-32 of the trailer.
+ *   mg_pngdec_inflate  : one wave per file; RFC 1951 in rounds of at most MG_PNGDEC_ROUND_TOKENS tokens (a stored block: one round per 2048 bytes).
+ *   mg_pngdec_unfilter : raw -> out uint8 [planes][h][w]; skips a file whose status is not 0.
+ * Each returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension. Every access is bounded by
+ * `data_bytes`, `raw_stride` and h, w; a record that does not fit them sets MG_PNGDEC_ST_RECORD.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_PNGDEC_THREADS 64
+#define MG_PNGDEC_REC_WORDS 72
+#define MG_PNGDEC_INFO_WORDS 8
+#define MG_PNGDEC_ROUND_TOKENS 64
+#define MG_PNGDEC_FLUSH_BYTES 4096
+#define MG_PNGDEC_MAX_SIDE 32767
+#define MG_PNGDEC_MAX_ROWBYTES 16384 /* the row that a band hands to the next stays in LDS */
+#define MG_PNGDEC_MAX_BYTES (1L << 28)
+#define MG_PNGDEC_MAX_RAW (1L << 30)
+#define MG_PNGDEC_ST_PAST_END 1    /* a read past the end of the stream */
+#define MG_PNGDEC_ST_SIZE 2        /* more or fewer bytes than h x (1 + rowbytes) */
+#define MG_PNGDEC_ST_DISTANCE 4    /* a distance beyond the bytes produced */
+#define MG_PNGDEC_ST_BLOCK_TYPE 8  /* the reserved block type */
+#define MG_PNGDEC_ST_STORED_LEN 16 /* LEN != ~NLEN */
+#define MG_PNGDEC_ST_CODE_SET 32   /* a code set that zlib refuses */
+#define MG_PNGDEC_ST_SYMBOL 64     /* an unassigned code, literal/length symbol 286 / 287 or distance symbol 30 / 31 */
+#define MG_PNGDEC_ST_ADLER 128     /* the Adler-32 of the inflated bytes is not the trailer's */
+#define MG_PNGDEC_ST_FILTER 256    /* a filter type above 4 */
+#define MG_PNGDEC_ST_INDEX 512     /* a palette index past PLTE's last entry */
+#define MG_PNGDEC_ST_RECORD 1024   /* a record outside data_bytes / raw_stride, or an unsupported colour type and depth */
+int mg_pngdec_limits(int* threads, int* max_side, int* max_rowbytes, int* rec_words, int* info_words, int* round_tokens, int* flush_bytes);
+int mg_pngdec_inflate(const uint8_t* data, long data_bytes, const int32_t* recs, uint8_t* raw, long raw_stride, int32_t* info, long planes, int h,
+                      int w, void* stream);
+int mg_pngdec_unfilter(const uint8_t* raw, long raw_stride, const int32_t* recs, uint8_t* out, int32_t* info, long planes, int h, int w,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

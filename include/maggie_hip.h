@@ -1169,6 +1169,39 @@ int mg_pngdec_inflate(const uint8_t* data, long data_bytes, const int32_t* recs,
 int mg_pngdec_unfilter(const uint8_t* raw, long raw_stride, const int32_t* recs, uint8_t* out, int32_t* info, long planes, int h, int w,
                        void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * PNG encoding (csrc/pngenc.hip): `nplanes` planes of one size [nplanes][h][w] -> the zlib streams (78 01, deflate, Adler-32) of 8-bit
+ * greyscale, non-interlaced PNG files, Sub filter on every row, packed back to back. Replaces the pixel pass of the result writer
+ * (maggie/engine/test.py:20-68). The host adds the signature, IHDR, the IDAT length and CRC, and IEND. DESIGN.md section 27.
+ *   mode    : MG_PNGENC_MODE_U8 uint8 samples; _UNIT float32, byte = (uint8)(x * 255.0f), NaN and x < 0 -> 0, x > 1 -> 255;
+ *             _THRESHOLD float32, byte = x > 0.5f ? 255 : 0. float planes 4-byte aligned.
+ *   blocks  : the filtered stream of a plane, h x (1 + w) bytes, is cut into ceil(h (1 + w) / MG_PNGENC_BLOCK_BYTES) deflate blocks; one
+ *             workgroup of MG_PNGENC_THREADS lanes per block. Tokens are runs (distance 1) inside a block.
+ *   recs    : int32 [nplanes][blocks][MG_PNGENC_REC_WORDS], written by mg_pngenc_size: [0] 1 fixed / 2 dynamic, [1] the block's bits (header
+ *             and end-of-block included), [2] its bytes, [3] its tokens, [4] sum b mod 65521, [5] sum (n - i) b_i mod 65521 (the Adler-32
+ *             partials), [6] literal/length codes sent, [7] code-length codes sent, [8..80) the 286 literal/length code lengths of the dynamic
+ *             construction as bytes, [80..85) the 19 code-length code lengths as bytes, the rest 0.
+ *   sizes   : int64 [nplanes], written by mg_pngenc_size: the bytes of each plane's zlib stream. 8-byte aligned.
+ *   mg_pngenc_emit : `out` zeroed by the caller, 16-byte aligned, `out_bytes` a multiple of 4 and at least the sum of `sizes`; plane p's
+ *             stream starts at the sum of sizes[0..p). Runs after mg_pngenc_size on the same stream with the same planes, recs and sizes.
+ * Each returns -2 for an argument error (before any launch: null or misaligned pointers, a mode, a side or a plane count out of range),
+ * -3 when nplanes x blocks exceeds 2^31 - 1. Every access is bounded by nplanes, h, w and out_bytes.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_PNGENC_THREADS 256
+#define MG_PNGENC_BLOCK_BYTES 16384
+#define MG_PNGENC_REC_WORDS 88
+#define MG_PNGENC_MAX_SIDE 32767             /* MG_PNGDEC_MAX_SIDE: the device decoder reads back what this writes */
+#define MG_PNGENC_MAX_WIDTH 16384            /* MG_PNGDEC_MAX_ROWBYTES */
+#define MG_PNGENC_MAX_RAW ((1L << 30) - 16)  /* h x (1 + w), as pngdec.parse accepts it */
+#define MG_PNGENC_MAX_PLANES 65536
+#define MG_PNGENC_MODE_U8 0
+#define MG_PNGENC_MODE_UNIT 1
+#define MG_PNGENC_MODE_THRESHOLD 2
+int mg_pngenc_limits(int* threads, int* block_bytes, int* rec_words, int* max_side, int* max_width, int* max_planes);
+int mg_pngenc_size(const void* planes, int mode, long nplanes, int h, int w, int32_t* recs, int64_t* sizes, void* stream);
+int mg_pngenc_emit(const void* planes, int mode, long nplanes, int h, int w, const int32_t* recs, const int64_t* sizes, uint8_t* out,
+                   long out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

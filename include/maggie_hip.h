@@ -1202,6 +1202,42 @@ int mg_pngenc_size(const void* planes, int mode, long nplanes, int h, int w, int
 int mg_pngenc_emit(const void* planes, int mode, long nplanes, int h, int w, const int32_t* recs, const int64_t* sizes, uint8_t* out,
                    long out_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Baseline JPEG encoding (csrc/jpegenc.hip): `frames` RGB frames of one size [frames][h][w][3] uint8 -> the entropy-coded segments (stuffed,
+ * with EOI) of the files Pillow's Image.save(path, quality=q) writes: 4:2:0, the Annex K Huffman tables, no optimisation, no restart markers.
+ * Replaces the pixel pass behind the synthesis tools' .save('....jpg') (tools/synthesize_image_him.py:93-109, synthesize_video_him.py:189).
+ * The host adds the 623 header bytes. DESIGN.md section 28. With mx = ceil(w / 16), my = ceil(h / 16): blocks = 6 mx my per frame.
+ *   lut, noise, qtab : the operands of mg_jpeg_ycc (lut uint8 [3][256] or null; noise int16 [h][w][noise_channels] or null; qtab int32 [2][64]
+ *             natural order, entries clamped to 1..255).
+ *   coef    : int16 [frames][blocks][64], 16-byte aligned, `coef_elems` = frames x blocks x 64: MCUs row by row, y0 y1 y2 y3 cb cr in an MCU,
+ *             natural order inside a block, DC terms NOT differenced -- the layout mg_jpegdec_dcsum leaves. A luma block beyond ceil(w / 8)
+ *             block columns or ceil(h / 8) block rows is a dummy block: AC terms 0, DC = the DC of the block before it in the MCU.
+ *   bits    : int32 [frames][blocks], the bits of each block in the scan; offs int64 [frames][blocks], their exclusive sum per frame.
+ *   sizes   : int64 [4][frames]: [0] the bytes of the frame's scan in the file (stuffed, + 2 for EOI), [1] its unstuffed bytes, [2] its bits,
+ *             [3] the exclusive sum of [0]: where the frame's scan starts in `out`. [1], [2] by mg_jpegenc_bits, [0], [3] by mg_jpegenc_pack.
+ *   raw     : uint8 [frames][raw_stride], ZEROED by the caller, 16-byte aligned: each frame's unstuffed stream at the start of its slice, the
+ *             last byte filled with 1-bits. raw_stride a multiple of 16, at least ceil(blocks x MG_JPEGENC_MAX_BLOCK_BITS / 8) + 4 rounded up to 16.
+ *   ffcount : int32 [frames][chunks], choff int64 [frames][chunks], chunks = ceil(raw_stride / MG_JPEGENC_CHUNK_BYTES): the 0xFF bytes of each
+ *             chunk of the unstuffed stream and their exclusive sum per frame (written for the chunks the stream reaches).
+ *   mg_jpegenc_stuff : raw -> out, a 0x00 behind every 0xFF, FF D9 behind the last byte; `out_bytes` bounds every store; `grid_chunks` in
+ *             1..chunks: the chunks launched per frame, at least ceil(max sizes[1] / MG_JPEGENC_CHUNK_BYTES).
+ * The entries run in this order on one stream. Each returns -2 for an argument error (before any launch: null or misaligned pointers, a size or a
+ * frame count out of range, a coef_elems or raw_stride that does not fit the geometry), -3 when a launch would exceed 2^31 - 1 workgroups.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_JPEGENC_THREADS 256
+#define MG_JPEGENC_PACK_BLOCKS 64        /* blocks of a packing workgroup: an LDS image of 64 x 1658 bits, 13 KiB */
+#define MG_JPEGENC_CHUNK_BYTES 4096      /* a stuffing chunk: 16 bytes a lane */
+#define MG_JPEGENC_MAX_BLOCK_BITS 1658   /* DC 9 + 11, 63 AC terms of 16 + 10 */
+#define MG_JPEGENC_MAX_FRAMES 4096
+int mg_jpegenc_limits(int* threads, int* pack_blocks, int* chunk_bytes, int* max_block_bits, int* max_side, int* max_frames);
+int mg_jpegenc_coef(const uint8_t* in, const uint8_t* lut, const int16_t* noise, int noise_channels, const int32_t* qtab, int16_t* coef,
+                    long coef_elems, long frames, int h, int w, void* stream);
+int mg_jpegenc_bits(const int16_t* coef, long coef_elems, int32_t* bits, int64_t* offs, int64_t* sizes, long frames, int h, int w, void* stream);
+int mg_jpegenc_pack(const int16_t* coef, long coef_elems, const int32_t* bits, const int64_t* offs, int64_t* sizes, uint8_t* raw, long raw_stride,
+                    int32_t* ffcount, int64_t* choff, long frames, int h, int w, void* stream);
+int mg_jpegenc_stuff(const uint8_t* raw, long raw_stride, const int64_t* choff, const int64_t* sizes, uint8_t* out, long out_bytes, long frames,
+                     int h, int w, long grid_chunks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

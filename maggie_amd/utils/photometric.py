@@ -14,7 +14,8 @@ between the flip and RandomAffine of a training item (maggie/dataloader/transfor
 
 The JPEG step is the lossy part of libjpeg-turbo at Pillow's defaults (baseline, 4:2:0, JDCT_ISLOW, no smoothing, fancy upsampling): colour
 conversion, edge replication, 2 x 2 downsampling, the integer forward DCT, quantisation, dequantisation, the integer inverse DCT, triangle
-upsampling and the conversion back. The entropy coding is lossless and is not built. Everything is int32 work or the IEEE divisions of
+upsampling and the conversion back. The entropy coding is lossless and has no part in the round trip; utils/jpegenc.py
+adds it where the file itself is wanted. Everything is int32 work or the IEEE divisions of
 Normalize: bit-exact against Pillow itself (tests/test_photometric_cpu.py holds the restatement the device is compared with against Pillow),
 no tolerance anywhere. A `PhotoDraws` moved to the device (`.to(device)`) makes `apply` upload nothing and never synchronise, so it can be
 captured in a graph and new values written into `lut`, `noise` and `qtable` between replays.

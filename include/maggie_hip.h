@@ -1238,6 +1238,40 @@ int mg_jpegenc_pack(const int16_t* coef, long coef_elems, const int32_t* bits, c
 int mg_jpegenc_stuff(const uint8_t* raw, long raw_stride, const int64_t* choff, const int64_t* sizes, uint8_t* out, long out_bytes, long frames,
                      int h, int w, long grid_chunks, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Matte output (csrc/matteout.hip): the pixel passes of the reference's predictor behind the forward (demo/maggie_predictor.py:35-40,62-76,
+ * 121-157; demo/app.py:58-65). DESIGN.md section 29. All four are compiled without floating-point contraction; none reads anything back or
+ * synchronises, so each can be captured in a graph. A lane owns MG_MATTE_GROUP consecutive pixels and moves them 16 bytes at a time; a base of
+ * any alignment is accepted (the 16-byte accesses then run unaligned), except where stated.
+ *   mg_matte_composite : alpha fp32 [frames * P][Hin][Win] (4-byte aligned) at the network's size -> per output pixel of [H][W] the bilinear
+ *             value (align_corners) over the top-left crop_h x crop_w region, as mg_postprocess_alpha states it but with every operation
+ *             rounded on its own; H == crop_h and W == crop_w copies the value bit for bit; nothing beyond the crop is read. `snap` != 0:
+ *             <= 1/255 -> 0, >= 254/255 -> 1. Then per channel of frames_u8 [frames][H][W][3]: t1 = f32(v) * a, t2 = (1 - a) * f32(bg),
+ *             s = t1 + t2, each rounded to fp32; out = trunc(clamp(s, 0, 255)), uint8 [frames * P][H][W][3]. The background is `bg_image`
+ *             uint8 [bg_frames][H][W][3] with bg_frames 1 (shared by all frames) or `frames`, or, when bg_image is null, the colour
+ *             (bg_r, bg_g, bg_b), each 0..255. `alpha_out`, when given, receives the fp32 [frames * P][H][W] alpha that was used. A frame's
+ *             bytes are loaded once for its P instances. Hin x Win and 3 H W must fit 31 bits.
+ *   mg_matte_overlay   : frames_u8 [frames][H][W][3], masks uint8 [frames][H][W], alpha in [0, 1] -> out [frames][H][W][3] =
+ *             trunc(f32(in1) + alpha * f32(in2 - in1)) with in2 = (r, g, b) where mask > 0, else 0: PIL.Image.blend(image, palette(mask), alpha).
+ *   mg_matte_label_ids : a label map of n elements, uint8 (elem_bytes 1) or int32 (elem_bytes 4) -> presence uint32
+ *             [MG_MATTE_PRESENCE_WORDS], zeroed by the call: bit (id & 31) of word (id >> 5) for every id 0..255 of the map; word 8 is
+ *             nonzero when an int32 label lies outside 0..255. An LDS bitmap per workgroup, ORed into the device words with atomics.
+ *   mg_matte_label_planes : planes uint8 [n_ids][n], 255 where the map equals ids[k], else 0; `ids` is a HOST array of n_ids <= 256 bytes.
+ * Each returns -2 for an argument error before any launch (a null pointer, a size, a crop, a colour, an alpha or an element size out of range,
+ * a misaligned fp32 or int32 base), -3 for more than 65535 frames in mg_matte_composite.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_MATTE_THREADS 256
+#define MG_MATTE_GROUP 16                /* pixels of a lane: 48 frame bytes, three 16-byte loads and stores */
+#define MG_MATTE_MAX_BLOCKS 16384        /* workgroups along x; the kernels stride over what is left */
+#define MG_MATTE_PRESENCE_WORDS 9
+int mg_matte_composite(const float* alpha, long frames, int P, int Hin, int Win, int crop_h, int crop_w, int H, int W, int snap,
+                       const uint8_t* frames_u8, const uint8_t* bg_image, long bg_frames, int bg_r, int bg_g, int bg_b, uint8_t* out,
+                       float* alpha_out, void* stream);
+int mg_matte_overlay(const uint8_t* frames_u8, const uint8_t* masks, long frames, int H, int W, int r, int g, int b, float alpha, uint8_t* out,
+                     void* stream);
+int mg_matte_label_ids(const void* map, int elem_bytes, long n, uint32_t* presence, void* stream);
+int mg_matte_label_planes(const void* map, int elem_bytes, long n, const uint8_t* ids, int n_ids, uint8_t* planes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1128,6 +1128,31 @@ int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long fram
                    const float* std3, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * Progressive JPEG decoding (csrc/jpegprog.hip): the scans of `frames` SOF2 files of one geometry -> the coefficient buffer of mg_jpegdec_idct
+ * (int16 [frames][blocks][64], zero-filled by the caller, DC terms final: mg_jpegdec_dcsum is NOT called). One wave per chain of scans
+ * (DESIGN.md section 30): a file's DC scans, or the AC scans of one of its components, in file order.
+ *   scans   : int32 [nscans][MG_JPEGPROG_SCAN_WORDS], one record per scan: two Huffman tables of 228 words each (mg_jpegdec's form; a DC scan:
+ *             DC table 0 and 1, an AC scan: its one table first); word 456 the segment's offset in `data`, 457 its length, 458 the restart
+ *             interval in MCUs (0 = none), 459 Ss, 460 Se, 461 Ah, 462 Al, 463 the blocks of an MCU of this scan when it is interleaved (0: one
+ *             component, visited over its real blocks in raster order), 464 that one component, 466..471 the interleaved scan's blocks:
+ *             slot in the frame's MCU | component << 4 | table << 8.
+ *   chains  : int32 [nchains][MG_JPEGPROG_CHAIN_WORDS]: frame, first scan record, number of scan records (run in that order), 0.
+ *   info    : int32 [frames], zeroed by the caller: the status bits of the frame's chains. A chain ends at its first status bit.
+ * An AC chain never stores coefficient 0, a DC chain nothing else, every store is 16 bits wide: all chains may share one launch.
+ * Returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension; `data_bytes`, `nscans`,
+ * `coef_elems` and the geometry bound every access, and a record that does not fit them sets MG_JPEGPROG_ST_RECORD.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_JPEGPROG_THREADS 64
+#define MG_JPEGPROG_SCAN_WORDS 480
+#define MG_JPEGPROG_CHAIN_WORDS 4
+#define MG_JPEGPROG_ST_REFINE 32  /* a refinement symbol whose size is not 1, or a new value past the end of the band */
+#define MG_JPEGPROG_ST_EXTRA 64   /* whole bytes of a scan's segment left behind its last block */
+#define MG_JPEGPROG_ST_RECORD 128 /* a scan or chain record outside the buffers or the geometry */
+int mg_jpegprog_limits(int* threads, int* scan_words, int* chain_words);
+int mg_jpegprog_chains(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
+                       long coef_elems, int32_t* info, long frames, int h, int w, int layout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * PNG decoding (csrc/pngdec.hip): the zlib streams (concatenated IDAT payloads) of `planes` non-interlaced files of one size -> the L plane of
  * Image.open(path).convert("L") on the device. Replaces the alpha / mask half of T.Load (maggie/dataloader/transforms.py:47-50). DESIGN.md
  * section 26. Colour type 0 and 3 at depth 1, 2, 4, 8; colour type 2, 4, 6 at depth 8.

@@ -1153,6 +1153,36 @@ int mg_jpegprog_chains(const uint8_t* data, long data_bytes, const int32_t* scan
                        long coef_elems, int32_t* info, long frames, int h, int w, int layout, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * JPEG decoding of the other chroma samplings: 4:2:2, 4:4:0 and 4:1:1, that is luma sampling (hs, vs) = (2, 1), (1, 2),
+ * (4, 1) over (1, 1) Cb and Cr. Each entry is its namesake above with `int hs, int vs` where that one takes `int layout`, runs the same kernels,
+ * and takes the same buffers; the entries above keep refusing every layout but their three. What differs is the geometry:
+ *   an MCU is 8 hs x 8 vs pixels and holds hs * vs luma blocks (row-major) then Cb then Cr: 4, 4, 6 blocks, the slot words 912..917 of `tabs`;
+ *   mcux = ceil(w / 8 hs), mcuy = ceil(h / 8 vs); coef int16 [frames][mcuy * mcux * (hs * vs + 2)][64];
+ *   planes  : Y [frames][mcuy * 8 vs][yp] then Cb, Cr [frames][mcuy * 8][cp] each, with the row pitches yp = mcux * 8 hs rounded up to 16 and
+ *             cp = mcux * 8, in 4:4:0 rounded up to 16: a lane of mg_jpeg_rgb_hv loads 16 luma and 8 / 16 / 4 chroma bytes at once, and a pitch
+ *             of that many bytes keeps each load inside its row and aligned. The bytes between a row's blocks and its pitch are never written
+ *             and never used. plane_bytes = frames * mcuy * 8 * (vs * yp + 2 * cp); `planes` 16-byte aligned.
+ *   mg_jpeg_rgb_hv (csrc/photometric.hip): the planes -> out with the epilogues of mg_jpeg_rgb. Chroma is upsampled over the real
+ *             ceil(h / vs) x ceil(w / hs) samples, neighbours clamped to them: 4:2:2 out[2j] = (3 c[j] + c[j-1] + 1) >> 2, out[2j+1] =
+ *             (3 c[j] + c[j+1] + 2) >> 2 along the row (replication when ceil(w / 2) <= 2); 4:4:0 the same along the column at every width;
+ *             4:1:1 replication.
+ * Each returns -2 for any other (hs, vs) and for every bad size or buffer (before any launch), -3 when the launch would exceed a grid dimension.
+ * ------------------------------------------------------------------------------------------------------------- */
+int mg_jpegdec_sync_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts,
+                       unsigned long long* entries, unsigned long long* bounds, int32_t* info, int info_words, long frames, int nsub, int sub_bytes,
+                       int hs, int vs, int launch, void* stream);
+int mg_jpegdec_coef_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
+                       int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h, int w, int hs,
+                       int vs, void* stream);
+int mg_jpegdec_dcsum_hv(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int hs, int vs, void* stream);
+int mg_jpegdec_idct_hv(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h, int w, int hs,
+                       int vs, void* stream);
+int mg_jpeg_rgb_hv(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int hs, int vs, int epilogue, const float* mean3,
+                   const float* std3, void* stream);
+int mg_jpegprog_chains_hv(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
+                          long coef_elems, int32_t* info, long frames, int h, int w, int hs, int vs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * PNG decoding (csrc/pngdec.hip): the zlib streams (concatenated IDAT payloads) of `planes` non-interlaced files of one size -> the L plane of
  * Image.open(path).convert("L") on the device. Replaces the alpha / mask half of T.Load (maggie/dataloader/transforms.py:47-50). DESIGN.md
  * section 26. Colour type 0 and 3 at depth 1, 2, 4, 8; colour type 2, 4, 6 at depth 8.

@@ -74,14 +74,23 @@ __device__ __forceinline__ int range_limit(int v) {
     return i < 128 ? i + 128 : (i < 512 ? 255 : (i < 896 ? 0 : i - 896));
 }
 
-struct Geo { int bpm, mcux, mcuy, hs; };                                   // blocks per MCU, the MCU grid, luma blocks per MCU side
-__host__ __device__ __forceinline__ Geo geo_of(int layout, int h, int w) {
+// blocks per MCU, the MCU grid, luma blocks per MCU row and column, the row pitch of the luma plane and of a chroma plane in bytes
+struct Geo { int bpm, mcux, mcuy, hs, vs, yp, cp; };
+// luma sampling (hs, vs) over (1, 1) chroma (`ncomp` 3), or one component. The 4:2:0 / 4:4:4 / grey planes are as wide as their blocks; the
+// planes of mg_jpeg_rgb_hv are pitched so that a lane's widest load stays inside its row: luma to 16 bytes, 4:4:0 chroma (16 samples a lane) too
+__host__ __device__ __forceinline__ Geo geo_hv(int hs, int vs, int ncomp, int h, int w, bool pitched) {
     Geo g;
-    g.hs = layout == MG_JPEGDEC_420 ? 2 : 1;
-    g.bpm = layout == MG_JPEGDEC_420 ? 6 : (layout == MG_JPEGDEC_444 ? 3 : 1);
-    g.mcux = (w + 8 * g.hs - 1) / (8 * g.hs);
-    g.mcuy = (h + 8 * g.hs - 1) / (8 * g.hs);
+    g.hs = hs; g.vs = vs;
+    g.bpm = ncomp == 1 ? 1 : hs * vs + 2;
+    g.mcux = (w + 8 * hs - 1) / (8 * hs);
+    g.mcuy = (h + 8 * vs - 1) / (8 * vs);
+    g.yp = g.mcux * 8 * hs; g.cp = g.mcux * 8;
+    if (pitched) { g.yp = (g.yp + 15) & ~15; if (vs == 2) g.cp = (g.cp + 15) & ~15; }
     return g;
+}
+__host__ __device__ __forceinline__ Geo geo_of(int layout, int h, int w) {
+    const int hs = layout == MG_JPEGDEC_420 ? 2 : 1;
+    return geo_hv(hs, hs, layout == MG_JPEGDEC_GREY ? 1 : 3, h, w, false);
 }
 
 // ---- the bit reader and one subsequence ------------------------------------------------------------------------------------------------------
@@ -348,7 +357,7 @@ __global__ __launch_bounds__(PT) void jd_dcsum_kernel(int16_t* __restrict__ coef
 }
 
 __global__ __launch_bounds__(PT) void jd_idct_kernel(const int16_t* __restrict__ coef, const int32_t* __restrict__ tabs, uint8_t* __restrict__ planes,
-                                                     long frames, int layout, Geo g, long nblocks) {
+                                                     long frames, Geo g, long nblocks) {
     __shared__ int s_blk[(PT / 8) * BP];
     const int tid = threadIdx.x, b = tid >> 3, l = tid & 7;
     const long u = (long)blockIdx.x * (PT / 8) + b;
@@ -356,7 +365,7 @@ __global__ __launch_bounds__(PT) void jd_idct_kernel(const int16_t* __restrict__
     const int bpf = g.mcux * g.mcuy * g.bpm;
     const long t = on ? u / bpf : 0;
     const int rb = on ? (int)(u - t * bpf) : 0, mcu = rb / g.bpm, slot = rb - mcu * g.bpm;
-    const int ny = g.hs * g.hs, c = slot < ny ? 0 : slot - ny + 1;
+    const int ny = g.hs * g.vs, c = slot < ny ? 0 : slot - ny + 1;
     int* __restrict__ blk = s_blk + b * BP;
     int d[8];
     if (on) {
@@ -380,11 +389,11 @@ __global__ __launch_bounds__(PT) void jd_idct_kernel(const int16_t* __restrict__
             hi |= (uint32_t)range_limit(d[k + 4]) << (8 * k);
         }
         const int my = mcu / g.mcux, mx = mcu - my * g.mcux;
-        const long pw = (long)g.mcux * 8 * g.hs, ph = (long)g.mcuy * 8 * g.hs;                    // the luma plane
+        const long pw = g.yp, ph = (long)g.mcuy * 8 * g.vs;                                      // the luma plane
         uint8_t* dst;
-        if (c == 0) dst = planes + (t * ph + (my * g.hs + slot / g.hs) * 8 + l) * pw + (mx * g.hs + slot % g.hs) * 8;
+        if (c == 0) dst = planes + (t * ph + (my * g.vs + slot / g.hs) * 8 + l) * pw + (mx * g.hs + slot % g.hs) * 8;
         else {
-            const long cw = pw / g.hs, chh = ph / g.hs;
+            const long cw = g.cp, chh = (long)g.mcuy * 8;
             dst = planes + frames * ph * pw + (c - 1) * (frames * chh * cw) + (t * chh + my * 8 + l) * cw + mx * 8;
         }
         *(uint2*)dst = make_uint2(lo, hi);
@@ -426,6 +435,61 @@ long plane_bytes_of(long frames, int layout, const Geo& g) {
     const long luma = (long)g.mcux * g.mcuy * 64 * g.hs * g.hs;
     return frames * (layout == MG_JPEGDEC_GREY ? luma : (layout == MG_JPEGDEC_444 ? 3 * luma : luma + luma / 2));
 }
+bool bad_hv(int hs, int vs) { return !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1)); }
+long plane_bytes_hv(long frames, const Geo& g) { return frames * (long)g.mcuy * 8 * ((long)g.vs * g.yp + 2L * g.cp); }
+
+// the launches behind the entry points, the geometry given: the layout entries and the (hs, vs) entries share them
+int launch_sync(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts, unsigned long long* entries,
+                unsigned long long* bounds, int32_t* info, long frames, int nsub, int sub_bytes, int bpm, int launch, void* stream) {
+    if (!data || !tabs || !exits || !counts || !entries || !bounds || !info) return -2;
+    const int wgs = (nsub + NT - 1) / NT;
+    if (frames > 0x7fffffffL / wgs) return -3;
+    hipLaunchKernelGGL(jd_sync_kernel, dim3((unsigned)(frames * wgs)), dim3(NT), 0, (hipStream_t)stream, data, data_bytes, tabs, exits, counts, entries,
+                       bounds, info, nsub, sub_bytes, wgs, bpm, frames, launch);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_coef(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
+                int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, const Geo& g, void* stream) {
+    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
+    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
+    if (frames == 0) return 0;
+    if (!data || !tabs || !exits || !counts || !first_block || !coef || !info) return -2;
+    const int wgs = (nsub + NT - 1) / NT;
+    if (frames > 0x7fffffffL / wgs) return -3;
+    hipLaunchKernelGGL(jd_prefix_kernel, dim3((unsigned)frames), dim3(PT), 0, (hipStream_t)stream, counts, first_block, nsub);
+    MG_CHECK_LAUNCH();
+    hipLaunchKernelGGL(jd_coef_kernel, dim3((unsigned)(frames * wgs)), dim3(NT), 0, (hipStream_t)stream, data, data_bytes, tabs, exits, first_block,
+                       coef, info, nsub, sub_bytes, wgs, g.bpm, (int)nbf);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_dcsum(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, const Geo& g, void* stream) {
+    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
+    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
+    if (frames == 0) return 0;
+    if (!coef || !tabs) return -2;
+    const int ncomp = g.bpm == 1 ? 1 : 3;
+    if (frames > 0x7fffffffL / ncomp) return -3;
+    hipLaunchKernelGGL(jd_dcsum_kernel, dim3((unsigned)(frames * ncomp)), dim3(PT), 0, (hipStream_t)stream, coef, tabs, g.bpm, g.mcux * g.mcuy, ncomp);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
+
+int launch_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long want_bytes, long frames,
+                const Geo& g, void* stream) {
+    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
+    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64 || plane_bytes != want_bytes) return -2;
+    if (frames == 0) return 0;
+    if (!coef || !tabs || !planes || (uintptr_t)planes % 16 != 0) return -2;
+    const long nblocks = frames * nbf, blocks = (nblocks + PT / 8 - 1) / (PT / 8);
+    if (blocks > 0x7fffffffL) return -3;
+    hipLaunchKernelGGL(jd_idct_kernel, dim3((unsigned)blocks), dim3(PT), 0, (hipStream_t)stream, coef, tabs, planes, frames, g, nblocks);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
 
 }  // namespace
 
@@ -441,62 +505,55 @@ extern "C" int mg_jpegdec_sync(const uint8_t* data, long data_bytes, const int32
     if (frames < 0 || bad_layout(layout) || bad_sub(nsub, sub_bytes) || data_bytes < 0 || launch < 0 || info_words < 4 ||
         launch > (info_words - 4) / 2) return -2;
     if (frames == 0) return 0;
-    if (!data || !tabs || !exits || !counts || !entries || !bounds || !info) return -2;
-    const int wgs = (nsub + NT - 1) / NT;
-    if (frames > 0x7fffffffL / wgs) return -3;
-    const Geo g = geo_of(layout, 8, 8);
-    hipLaunchKernelGGL(jd_sync_kernel, dim3((unsigned)(frames * wgs)), dim3(NT), 0, (hipStream_t)stream, data, data_bytes, tabs, exits, counts, entries,
-                       bounds, info, nsub, sub_bytes, wgs, g.bpm, frames, launch);
-    MG_CHECK_LAUNCH();
-    return 0;
+    return launch_sync(data, data_bytes, tabs, exits, counts, entries, bounds, info, frames, nsub, sub_bytes, geo_of(layout, 8, 8).bpm, launch, stream);
+}
+
+extern "C" int mg_jpegdec_sync_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts,
+                                  unsigned long long* entries, unsigned long long* bounds, int32_t* info, int info_words, long frames, int nsub,
+                                  int sub_bytes, int hs, int vs, int launch, void* stream) {
+    if (frames < 0 || bad_hv(hs, vs) || bad_sub(nsub, sub_bytes) || data_bytes < 0 || launch < 0 || info_words < 4 ||
+        launch > (info_words - 4) / 2) return -2;
+    if (frames == 0) return 0;
+    return launch_sync(data, data_bytes, tabs, exits, counts, entries, bounds, info, frames, nsub, sub_bytes, hs * vs + 2, launch, stream);
 }
 
 extern "C" int mg_jpegdec_coef(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
                                int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h, int w,
                                int layout, void* stream) {
     if (bad_size(frames, h, w) || bad_layout(layout) || bad_sub(nsub, sub_bytes) || data_bytes < 0) return -2;
-    const Geo g = geo_of(layout, h, w);
-    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
-    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
-    if (frames == 0) return 0;
-    if (!data || !tabs || !exits || !counts || !first_block || !coef || !info) return -2;
-    const int wgs = (nsub + NT - 1) / NT;
-    if (frames > 0x7fffffffL / wgs) return -3;
-    hipLaunchKernelGGL(jd_prefix_kernel, dim3((unsigned)frames), dim3(PT), 0, (hipStream_t)stream, counts, first_block, nsub);
-    MG_CHECK_LAUNCH();
-    hipLaunchKernelGGL(jd_coef_kernel, dim3((unsigned)(frames * wgs)), dim3(NT), 0, (hipStream_t)stream, data, data_bytes, tabs, exits, first_block,
-                       coef, info, nsub, sub_bytes, wgs, g.bpm, (int)nbf);
-    MG_CHECK_LAUNCH();
-    return 0;
+    return launch_coef(data, data_bytes, tabs, exits, counts, first_block, coef, coef_elems, info, frames, nsub, sub_bytes, geo_of(layout, h, w), stream);
+}
+
+extern "C" int mg_jpegdec_coef_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
+                                  int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h,
+                                  int w, int hs, int vs, void* stream) {
+    if (bad_size(frames, h, w) || bad_hv(hs, vs) || bad_sub(nsub, sub_bytes) || data_bytes < 0) return -2;
+    return launch_coef(data, data_bytes, tabs, exits, counts, first_block, coef, coef_elems, info, frames, nsub, sub_bytes,
+                       geo_hv(hs, vs, 3, h, w, true), stream);
 }
 
 extern "C" int mg_jpegdec_dcsum(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int layout, void* stream) {
     if (bad_size(frames, h, w) || bad_layout(layout)) return -2;
-    const Geo g = geo_of(layout, h, w);
-    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
-    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
-    if (frames == 0) return 0;
-    if (!coef || !tabs) return -2;
-    const int ncomp = layout == MG_JPEGDEC_GREY ? 1 : 3;
-    if (frames > 0x7fffffffL / ncomp) return -3;
-    hipLaunchKernelGGL(jd_dcsum_kernel, dim3((unsigned)(frames * ncomp)), dim3(PT), 0, (hipStream_t)stream, coef, tabs, g.bpm, g.mcux * g.mcuy, ncomp);
-    MG_CHECK_LAUNCH();
-    return 0;
+    return launch_dcsum(coef, coef_elems, tabs, frames, geo_of(layout, h, w), stream);
+}
+
+extern "C" int mg_jpegdec_dcsum_hv(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int hs, int vs, void* stream) {
+    if (bad_size(frames, h, w) || bad_hv(hs, vs)) return -2;
+    return launch_dcsum(coef, coef_elems, tabs, frames, geo_hv(hs, vs, 3, h, w, true), stream);
 }
 
 extern "C" int mg_jpegdec_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h, int w,
                                int layout, void* stream) {
     if (bad_size(frames, h, w) || bad_layout(layout)) return -2;
     const Geo g = geo_of(layout, h, w);
-    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
-    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64 || plane_bytes != plane_bytes_of(frames, layout, g)) return -2;
-    if (frames == 0) return 0;
-    if (!coef || !tabs || !planes || (uintptr_t)planes % 16 != 0) return -2;
-    const long nblocks = frames * nbf, blocks = (nblocks + PT / 8 - 1) / (PT / 8);
-    if (blocks > 0x7fffffffL) return -3;
-    hipLaunchKernelGGL(jd_idct_kernel, dim3((unsigned)blocks), dim3(PT), 0, (hipStream_t)stream, coef, tabs, planes, frames, layout, g, nblocks);
-    MG_CHECK_LAUNCH();
-    return 0;
+    return launch_idct(coef, coef_elems, tabs, planes, plane_bytes, plane_bytes_of(frames, layout, g), frames, g, stream);
+}
+
+extern "C" int mg_jpegdec_idct_hv(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h,
+                                  int w, int hs, int vs, void* stream) {
+    if (bad_size(frames, h, w) || bad_hv(hs, vs)) return -2;
+    const Geo g = geo_hv(hs, vs, 3, h, w, true);
+    return launch_idct(coef, coef_elems, tabs, planes, plane_bytes, plane_bytes_hv(frames, g), frames, g, stream);
 }
 
 extern "C" int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int layout, int epilogue,

@@ -167,29 +167,32 @@ __device__ __forceinline__ void jp_restart(Bits& r, int done, int& status) {
     jp_open(r, r.rp + 2);
 }
 
-struct Geo { int bpm, mcux, mcuy, ncomp; };
-__host__ __device__ __forceinline__ Geo jp_geo(int layout, int h, int w) {
+struct Geo { int bpm, mcux, mcuy, ncomp, hl, vl; };                        // hl, vl: log2 of the luma blocks per MCU row and column
+// luma sampling (hs, vs), each 1, 2 or 4, over (1, 1) chroma, or one component
+__host__ __device__ __forceinline__ Geo jp_geo(int hs, int vs, int ncomp, int h, int w) {
     Geo g;
-    const int hs = layout == MG_JPEGDEC_420 ? 2 : 1;
-    g.bpm = layout == MG_JPEGDEC_420 ? 6 : (layout == MG_JPEGDEC_444 ? 3 : 1);
-    g.ncomp = layout == MG_JPEGDEC_GREY ? 1 : 3;
+    g.bpm = ncomp == 1 ? 1 : hs * vs + 2;
+    g.ncomp = ncomp;
+    g.hl = hs == 4 ? 2 : hs - 1;
+    g.vl = vs == 4 ? 2 : vs - 1;
     g.mcux = (w + 8 * hs - 1) / (8 * hs);
-    g.mcuy = (h + 8 * hs - 1) / (8 * hs);
+    g.mcuy = (h + 8 * vs - 1) / (8 * vs);
     return g;
 }
 
-// block (by, bx) of component `comp`, counted over the component's real blocks -> its index in the MCU-major buffer
-__device__ __forceinline__ long jp_at(int by, int bx, int comp, int layout, const Geo& g) {
-    if (layout == MG_JPEGDEC_420)
-        return comp == 0 ? ((long)(by >> 1) * g.mcux + (bx >> 1)) * 6 + (by & 1) * 2 + (bx & 1) : ((long)by * g.mcux + bx) * 6 + 3 + comp;
-    return layout == MG_JPEGDEC_444 ? ((long)by * g.mcux + bx) * 3 + comp : (long)by * g.mcux + bx;
+// block (by, bx) of component `comp`, counted over the component's real blocks -> its index in the MCU-major buffer: a luma block lives in MCU
+// (by / vs, bx / hs), slot (by % vs) * hs + bx % hs; the chroma slots follow the hs * vs luma slots
+__device__ __forceinline__ long jp_at(int by, int bx, int comp, const Geo& g) {
+    if (comp == 0)
+        return ((long)(by >> g.vl) * g.mcux + (bx >> g.hl)) * g.bpm + ((by & ((1 << g.vl) - 1)) << g.hl) + (bx & ((1 << g.hl) - 1));
+    return ((long)by * g.mcux + bx) * g.bpm + (1 << (g.hl + g.vl)) + comp - 1;
 }
 // the same for block n of the component's raster order (`bw` blocks per row)
-__device__ __forceinline__ long jp_block(int n, int bw, int comp, int layout, const Geo& g) { return jp_at(n / bw, n % bw, comp, layout, g); }
+__device__ __forceinline__ long jp_block(int n, int bw, int comp, const Geo& g) { return jp_at(n / bw, n % bw, comp, g); }
 
 // one scan of a chain; returns its status bits. `cf`: the frame's coefficients; `s_tab` / `s_win`: LDS.
 __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long data_bytes, const int32_t* __restrict__ rec, int16_t* __restrict__ cf,
-                                       int h, int w, int layout, const Geo& g, int* s_tab, uint8_t* s_win, int16_t* s_stage) {
+                                       int h, int w, const Geo& g, int* s_tab, uint8_t* s_win, int16_t* s_stage) {
     const int lane = threadIdx.x;
     __syncthreads();                                                       // the scan before is done with the LDS
     for (int k = lane; k < SW; k += NL) s_tab[k] = rec[k];
@@ -204,8 +207,8 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
         if ((sl & 15) >= g.bpm || ((sl >> 4) & 15) >= g.ncomp || (sl >> 8) < 0 || (sl >> 8) > 1) return MG_JPEGPROG_ST_RECORD;
     }
     // the units of the scan: MCUs when it is interleaved, else the component's real blocks in raster order
-    const int bw = nslot ? g.mcux : (layout == MG_JPEGDEC_420 && comp == 0 ? (w + 7) / 8 : g.mcux);
-    const int bh = nslot ? g.mcuy : (layout == MG_JPEGDEC_420 && comp == 0 ? (h + 7) / 8 : g.mcuy);
+    const int bw = nslot == 0 && comp == 0 ? (w + 7) / 8 : g.mcux;        // a chroma component has one block per MCU: its real blocks are the MCUs
+    const int bh = nslot == 0 && comp == 0 ? (h + 7) / 8 : g.mcuy;
     const int units = bw * bh, per = nslot ? nslot : 1;
     const int nat = JP_NATURAL[lane];
     Bits r;
@@ -232,7 +235,7 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
             for (int k = 0; k < per && status == 0; ++k) {
                 const int sl = nslot ? JP_UNI(s_tab[S_SLOT + k]) : (comp << 4);
                 const int c = (sl >> 4) & 15;
-                const long blk = nslot ? (long)unit * g.bpm + (sl & 15) : jp_block(unit, bw, comp, layout, g);
+                const long blk = nslot ? (long)unit * g.bpm + (sl & 15) : jp_block(unit, bw, comp, g);
                 const int s = jp_symbol(r, s_tab + HT * (sl >> 8), status);
                 if (s > 11) status |= MG_JPEGDEC_ST_CODE;
                 if (status) break;
@@ -247,7 +250,7 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
             const unsigned long long bits = jp_take_long(r, nb, status);
             if (status == 0 && lane < nb && ((bits >> (nb - 1 - lane)) & 1)) {
                 const int u = lane / per, k = lane - u * per;
-                const long blk = nslot ? (long)(unit + u) * g.bpm + (s_tab[S_SLOT + k] & 15) : jp_block(unit + u, bw, comp, layout, g);
+                const long blk = nslot ? (long)(unit + u) * g.bpm + (s_tab[S_SLOT + k] & 15) : jp_block(unit + u, bw, comp, g);
                 cf[blk * 64] = (int16_t)(cf[blk * 64] | p1);
             }
             unit += m; togo -= m;
@@ -259,7 +262,7 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
                 if (bx >= bw) { by += bx / bw; bx %= bw; }
                 continue;
             }
-            int16_t* __restrict__ p = cf + jp_at(by, bx, comp, layout, g) * 64;
+            int16_t* __restrict__ p = cf + jp_at(by, bx, comp, g) * 64;
             int k = Ss;
             for (int it = 0; it < 64 && k <= Se && status == 0; ++it) {
                 const int rs = jp_symbol(r, s_tab, status), rr = rs >> 4, s = rs & 15;
@@ -279,13 +282,13 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
             unit += 1; togo -= 1;
             if (++bx == bw) { bx = 0; by += 1; }
         } else {                                                           // ---- AC refinement
-            int16_t* __restrict__ p = cf + jp_at(by, bx, comp, layout, g) * 64;
+            int16_t* __restrict__ p = cf + jp_at(by, bx, comp, g) * 64;
             if (unit >= staged) {                                          // unit == staged: the cursor (qy, qx) is at this block
                 int v[AHEAD];
                 __syncthreads();
 #pragma unroll
                 for (int j = 0; j < AHEAD; ++j) {
-                    v[j] = band && staged + j < units ? (int)cf[jp_at(qy, qx, comp, layout, g) * 64 + nat] : 0;
+                    v[j] = band && staged + j < units ? (int)cf[jp_at(qy, qx, comp, g) * 64 + nat] : 0;
                     if (++qx == bw) { qx = 0; qy += 1; }
                 }
 #pragma unroll
@@ -352,7 +355,7 @@ __device__ __forceinline__ int jp_scan(const uint8_t* __restrict__ data, long da
 
 __global__ __launch_bounds__(NL) void jp_chain_kernel(const uint8_t* __restrict__ data, long data_bytes, const int32_t* __restrict__ scans, long nscans,
                                                       const int32_t* __restrict__ chains, int16_t* __restrict__ coef, int32_t* __restrict__ info,
-                                                      long frames, int h, int w, int layout, Geo g) {
+                                                      long frames, int h, int w, Geo g) {
     __shared__ int s_tab[SW];
     __shared__ uint32_t s_win32[WIN / 4 + 2];                               // jp_word reads the dword behind the window's last
     uint8_t* s_win = (uint8_t*)s_win32;
@@ -363,8 +366,26 @@ __global__ __launch_bounds__(NL) void jp_chain_kernel(const uint8_t* __restrict_
     int status = 0;
     if (first < 0 || n < 0 || first + n > nscans) status = MG_JPEGPROG_ST_RECORD;
     int16_t* __restrict__ cf = coef + t * (long)g.mcux * g.mcuy * g.bpm * 64;
-    for (long k = 0; k < n && status == 0; ++k) status = jp_scan(data, data_bytes, scans + (first + k) * SW, cf, h, w, layout, g, s_tab, s_win, s_stage);
+    for (long k = 0; k < n && status == 0; ++k) status = jp_scan(data, data_bytes, scans + (first + k) * SW, cf, h, w, g, s_tab, s_win, s_stage);
     if (status && threadIdx.x == 0) atomicOr(&info[t], status);
+}
+
+// the launch behind both entry points, the geometry given
+int jp_launch(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
+              long coef_elems, int32_t* info, long frames, int h, int w, const Geo& g, void* stream) {
+    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
+    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
+    if (frames == 0 || nchains == 0) return 0;
+    if (!data || !scans || !chains || !coef || !info) return -2;
+    if (nchains > 0x7fffffffL) return -3;
+    hipLaunchKernelGGL(jp_chain_kernel, dim3((unsigned)nchains), dim3(NL), 0, (hipStream_t)stream, data, data_bytes, scans, nscans, chains, coef, info,
+                       frames, h, w, g);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
+bool jp_bad(long data_bytes, long nscans, long nchains, long frames, int h, int w) {
+    return frames < 0 || h <= 0 || w <= 0 || h > MG_JPEG_MAX_SIDE || w > MG_JPEG_MAX_SIDE || data_bytes < 0 || data_bytes > MG_JPEGDEC_MAX_BYTES ||
+           nscans < 0 || nchains < 0;
 }
 
 }  // namespace
@@ -377,16 +398,14 @@ extern "C" int mg_jpegprog_limits(int* threads, int* scan_words, int* chain_word
 
 extern "C" int mg_jpegprog_chains(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains,
                                   int16_t* coef, long coef_elems, int32_t* info, long frames, int h, int w, int layout, void* stream) {
-    if (frames < 0 || h <= 0 || w <= 0 || h > MG_JPEG_MAX_SIDE || w > MG_JPEG_MAX_SIDE || data_bytes < 0 || data_bytes > MG_JPEGDEC_MAX_BYTES ||
-        nscans < 0 || nchains < 0 || (layout != MG_JPEGDEC_420 && layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY)) return -2;
-    const Geo g = jp_geo(layout, h, w);
-    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
-    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
-    if (frames == 0 || nchains == 0) return 0;
-    if (!data || !scans || !chains || !coef || !info) return -2;
-    if (nchains > 0x7fffffffL) return -3;
-    hipLaunchKernelGGL(jp_chain_kernel, dim3((unsigned)nchains), dim3(NL), 0, (hipStream_t)stream, data, data_bytes, scans, nscans, chains, coef, info,
-                       frames, h, w, layout, g);
-    MG_CHECK_LAUNCH();
-    return 0;
+    if (jp_bad(data_bytes, nscans, nchains, frames, h, w) || (layout != MG_JPEGDEC_420 && layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY)) return -2;
+    const int hs = layout == MG_JPEGDEC_420 ? 2 : 1;
+    return jp_launch(data, data_bytes, scans, nscans, chains, nchains, coef, coef_elems, info, frames, h, w,
+                     jp_geo(hs, hs, layout == MG_JPEGDEC_GREY ? 1 : 3, h, w), stream);
+}
+
+extern "C" int mg_jpegprog_chains_hv(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains,
+                                     int16_t* coef, long coef_elems, int32_t* info, long frames, int h, int w, int hs, int vs, void* stream) {
+    if (jp_bad(data_bytes, nscans, nchains, frames, h, w) || !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1))) return -2;
+    return jp_launch(data, data_bytes, scans, nscans, chains, nchains, coef, coef_elems, info, frames, h, w, jp_geo(hs, vs, 3, h, w), stream);
 }

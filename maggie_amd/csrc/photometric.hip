@@ -19,10 +19,15 @@
 //   ceil(h / 2) x ceil(w / 2) samples (neighbours clamped to them, never the padding), 2 x 2 replication when ceil(w / 2) <= 2, YCbCr -> RGB, clamp;
 //   three uint4 of raw bytes, or four float4 per channel plane with the Normalize epilogue of pixel_norm.h; per element on ragged widths and
 //   unaligned bases.
+// jpeg_rgb_hv_kernel the same for the planes mg_jpegdec_idct_hv leaves (luma sampling (2,1), (1,2) or (4,1) over (1,1) chroma, DESIGN.md section
+//   31): 16 luma bytes and 8 / 2 x 16 / 4 chroma bytes per lane in one load each; 4:2:2 the triangle filter along the row (replication when
+//   ceil(w / 2) <= 2), 4:4:0 along the column at every width, 4:1:1 replication; neighbours clamped to the real samples.
 // photo_point_kernel the tone curve and / or the saturating add alone, the same 16 pixels per lane and the same two epilogues.
+#ifndef MG_HOST_EMU
 #include "common.h"
 #include "../../include/maggie_hip.h"
 #include "pixel_norm.h"
+#endif
 
 namespace {
 
@@ -289,6 +294,65 @@ __global__ __launch_bounds__(PT) void jpeg_rgb_kernel(const uint8_t* __restrict_
     store16<EPI>(px, out, t, y, x0, n, h, w, vec, mean, std);
 }
 
+// planes as mg_jpegdec_idct_hv leaves them: Y [T][ph][yp], Cb and Cr [T][chh][cp]; yp is a multiple of 16 and cp of the chroma bytes a lane loads,
+// so that every load below lies inside its row and is aligned to its own size
+template <int EPI, int HS, int VS>
+__global__ __launch_bounds__(PT) void jpeg_rgb_hv_kernel(const uint8_t* __restrict__ planes, void* __restrict__ out, long frames, int h, int w, int ph,
+                                                         int yp, int chh, int cp, int groups, long units, int vec, float m0, float m1, float m2,
+                                                         float s0, float s1, float s2) {
+    const long u = (long)blockIdx.x * PT + threadIdx.x;
+    if (u >= units) return;
+    const long row = u / groups, t = row / h;
+    const int y = (int)(row - t * h), x0 = (int)(u - row * groups) * 16, n = min(16, w - x0);
+    const int chr = (h + VS - 1) / VS, cwr = (w + HS - 1) / HS;          // the real chroma samples
+    const uint4 yv = *(const uint4*)(planes + (t * ph + y) * (long)yp + x0);                        // x0 + 15 < yp
+    const uint32_t yw[4] = {yv.x, yv.y, yv.z, yv.w};
+    int c16[2][16];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const uint8_t* __restrict__ plane = planes + frames * (long)ph * yp + c * (frames * (long)chh * cp) + t * (long)chh * cp;
+        if constexpr (HS == 2) {                                           // 4:2:2: columns j0 - 1 .. j0 + 8 of this row among the real columns
+            const uint8_t* __restrict__ ra = plane + (long)y * cp;
+            const int j0 = x0 >> 1, jl = max(j0 - 1, 0), jr = min(j0 + 8, cwr - 1);
+            const uint2 a = *(const uint2*)(ra + j0);                      // j0 + 7 < cp
+            int p[10];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) p[k + 1] = (int)(((k < 4 ? a.x : a.y) >> (8 * (k & 3))) & 255u);
+            p[0] = ra[jl];
+            p[9] = ra[jr];
+            const bool fancy = cwr > 2;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int j = j0 + k, cur = p[k + 1];
+                const int left = j == 0 ? cur : p[k], right = j >= cwr - 1 ? cur : p[k + 2];
+                c16[c][2 * k] = fancy ? (3 * cur + left + 1) >> 2 : cur;
+                c16[c][2 * k + 1] = fancy ? (3 * cur + right + 2) >> 2 : cur;
+            }
+        } else if constexpr (VS == 2) {                                    // 4:4:0: the row's chroma row and its neighbour among the REAL rows
+            const int i = y >> 1, inb = (y & 1) ? min(i + 1, chr - 1) : max(i - 1, 0), bias = 1 + (y & 1);
+            const uint4 a = *(const uint4*)(plane + (long)i * cp + x0), b = *(const uint4*)(plane + (long)inb * cp + x0);      // x0 + 15 < cp
+            const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, bw[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                c16[c][k] = (3 * (int)((aw[k >> 2] >> (8 * (k & 3))) & 255u) + (int)((bw[k >> 2] >> (8 * (k & 3))) & 255u) + bias) >> 2;
+        } else {                                                           // 4:1:1: four columns of this row, each four times
+            const uint32_t a = *(const uint32_t*)(plane + (long)y * cp + (x0 >> 2));               // x0 / 4 + 3 < cp
+#pragma unroll
+            for (int k = 0; k < 16; ++k) c16[c][k] = (int)((a >> (8 * (k >> 2))) & 255u);
+        }
+    }
+    int px[16][3];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+        const int Y = (int)((yw[j >> 2] >> (8 * (j & 3))) & 255u), cb = c16[0][j] - 128, cr = c16[1][j] - 128;
+        px[j][0] = clamp255(Y + ((91881 * cr + 32768) >> 16));
+        px[j][1] = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+        px[j][2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
+    }
+    const float mean[3] = {m0, m1, m2}, std[3] = {s0, s1, s2};
+    store16<EPI>(px, out, t, y, x0, n, h, w, vec, mean, std);
+}
+
 template <int EPI>
 __global__ __launch_bounds__(PT) void photo_point_kernel(const uint8_t* __restrict__ in, void* __restrict__ out, const uint8_t* __restrict__ lut,
                                                          const int16_t* __restrict__ noise, int nc, int h, int w, int groups, long units, int vin,
@@ -377,6 +441,38 @@ extern "C" int mg_jpeg_rgb(const uint8_t* planes, void* out, long frames, int h,
     else
         hipLaunchKernelGGL(jpeg_rgb_kernel<MG_PHOTO_NORM>, dim3((unsigned)blocks), dim3(PT), 0, (hipStream_t)stream, planes, out, frames, h, w, h16, w16,
                            groups, units, vec, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    MG_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int mg_jpeg_rgb_hv(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int hs, int vs, int epilogue,
+                              const float* mean3, const float* std3, void* stream) {
+    if (bad_size(frames, h, w) || bad_epilogue(epilogue) || !mean3 || !std3 || !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1)))
+        return -2;
+    // mg_jpegdec_idct_hv's planes: whole MCUs, the luma pitch a multiple of 16, the 4:4:0 chroma pitch too
+    const int mcux = (w + 8 * hs - 1) / (8 * hs), mcuy = (h + 8 * vs - 1) / (8 * vs);
+    const int ph = mcuy * 8 * vs, yp = (mcux * 8 * hs + 15) & ~15, chh = mcuy * 8, cp = vs == 2 ? (mcux * 8 + 15) & ~15 : mcux * 8;
+    if (plane_bytes != frames * ((long)ph * yp + 2L * chh * cp)) return -2;
+    if (frames == 0) return 0;
+    if (!planes || !out || (const void*)planes == out || (uintptr_t)planes % 16 != 0) return -2;
+    const int groups = (w + 15) / 16;
+    if (frames > 0x7fffffffffL / ((long)h * groups)) return -3;
+    const long units = frames * h * groups, blocks = (units + PT - 1) / PT;
+    if (blocks > 0x7fffffffL) return -3;
+    const int vec = vec_ok(out, w);
+#define MG_RGB_HV(E, H, V)                                                                                                                         \
+    hipLaunchKernelGGL((jpeg_rgb_hv_kernel<E, H, V>), dim3((unsigned)blocks), dim3(PT), 0, (hipStream_t)stream, planes, out, frames, h, w, ph, yp, \
+                       chh, cp, groups, units, vec, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2])
+    if (epilogue == MG_PHOTO_RAW) {
+        if (hs == 2) MG_RGB_HV(MG_PHOTO_RAW, 2, 1);
+        else if (vs == 2) MG_RGB_HV(MG_PHOTO_RAW, 1, 2);
+        else MG_RGB_HV(MG_PHOTO_RAW, 4, 1);
+    } else {
+        if (hs == 2) MG_RGB_HV(MG_PHOTO_NORM, 2, 1);
+        else if (vs == 2) MG_RGB_HV(MG_PHOTO_NORM, 1, 2);
+        else MG_RGB_HV(MG_PHOTO_NORM, 4, 1);
+    }
+#undef MG_RGB_HV
     MG_CHECK_LAUNCH();
     return 0;
 }

@@ -61,8 +61,25 @@ class JpegPlan:
         return ((self.width + side - 1) // side) * ((self.height + side - 1) // side)
 
 
+def _layout(sampling):
+    """The layout of a frame's ((h, v) per component), or `Unsupported`: what this module and `jpegprog` decode."""
+    if len(sampling) == 1:
+        return GREY
+    if sampling == ((2, 2), (1, 1), (1, 1)):
+        return L420
+    if sampling == ((1, 1), (1, 1), (1, 1)):
+        return L444
+    raise Unsupported('sampling %s (only 4:2:0 and 4:4:4 are decoded)' % (sampling,))
+
+
 def parse(data):
     """The marker walk of one file's bytes -> JpegPlan. Host only; raises `Unsupported` by name for what the device does not decode."""
+    return _parse(data, _layout)
+
+
+def _parse(data, layout_of):
+    """`parse` with the accepted samplings given: `layout_of(sampling)` returns the layout or raises `Unsupported` (`jpegsamp.parse` walks the
+    same markers for its three samplings)."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
     d = bytes(data)
@@ -164,14 +181,7 @@ def parse(data):
     if [c[0] for c in comps] != [s[0] for s in scan]:
         raise Unsupported('several scans, or a scan that does not hold every component in frame order')
     sampling = tuple((c[1], c[2]) for c in comps)
-    if len(comps) == 1:
-        layout = GREY
-    elif sampling == ((2, 2), (1, 1), (1, 1)):
-        layout = L420
-    elif sampling == ((1, 1), (1, 1), (1, 1)):
-        layout = L444
-    else:
-        raise Unsupported('sampling %s (only 4:2:0 and 4:4:4 are decoded)' % (sampling,))
+    layout = layout_of(sampling)
     for c in comps:
         if c[3] not in quant:
             raise Unsupported('quantisation table %d is not defined' % c[3])
@@ -245,7 +255,8 @@ def record(plan, offset):
     for k, t in enumerate((plan.dc.get(0, empty), plan.dc.get(1, empty), plan.ac.get(0, empty), plan.ac.get(1, empty))):
         rec[228 * k:228 * (k + 1)] = huffman_words(*t)
     sel = plan.selectors
-    slots = [sel[0]] * 4 + [sel[1], sel[2]] if plan.layout == L420 else list(sel)
+    hs, vs = plan.sampling[0]                                  # an MCU: the hs * vs luma blocks, then Cb, then Cr
+    slots = [sel[0]] * (hs * vs) + [sel[1], sel[2]] if len(sel) == 3 else list(sel)
     for s, (td, ta) in enumerate(slots):
         rec[912 + s] = td | (ta << 4)
     rec[918], rec[919], rec[920] = offset + plan.offset, plan.length, plan.restart_interval
@@ -273,9 +284,18 @@ class Decoded:
     `readbacks`."""
 
 
-def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+def hv_geometry(h, w, hs, vs):
+    """The geometry of the `_hv` entries (include/maggie_hip.h): (blocks of a frame, plane bytes of a frame, luma rows, luma pitch, chroma
+    rows, chroma pitch). The luma pitch is a multiple of 16 bytes and the 4:4:0 chroma pitch too: the widest load of a lane of mg_jpeg_rgb_hv."""
+    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
+    yp, cp = -(-mx * 8 * hs // 16) * 16, -(-mx * 8 // 16) * 16 if vs == 2 else mx * 8
+    return mx * my * (hs * vs + 2), my * 8 * (vs * yp + 2 * cp), my * 8 * vs, yp, my * 8, cp
+
+
+def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, hv=None):
     """The launches themselves: `blob` uint8 device tensor holding the T segments, `recs` int32 (T, TAB_WORDS) host records whose offsets point
-    into it. `out`: a preallocated contiguous destination of the right size and dtype (else allocated). Returns a `Decoded`."""
+    into it. `out`: a preallocated contiguous destination of the right size and dtype (else allocated). `hv`: the luma sampling (hs, vs) of
+    `jpegsamp`'s layouts, which run the `_hv` entries (`layout` is then not passed on). Returns a `Decoded`."""
     S = _sub_bytes(sub_bytes)
     recs = np.ascontiguousarray(recs, np.int32).reshape(-1, TAB_WORDS)
     T = recs.shape[0]
@@ -296,10 +316,17 @@ def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGE
     entries = torch.empty((T, wgs), dtype=torch.int64, device=dev)
     bounds = torch.zeros((2, T, wgs), dtype=torch.int64, device=dev)
     info = torch.zeros((4 + 2 * (max_launches + 1),), dtype=torch.int32, device=dev)
-    nblocks = ((w + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * \
-        ((h + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * BLOCKS_PER_MCU[layout]
+    if hv is None:
+        nblocks = ((w + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * \
+            ((h + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * BLOCKS_PER_MCU[layout]
+        nplanes = planes_size(T, h, w, layout)
+        sfx, geo = '', (c_int(layout),)
+    else:
+        nblocks, per_frame = hv_geometry(h, w, *hv)[:2]
+        nplanes = T * per_frame
+        sfx, geo = '_hv', (c_int(hv[0]), c_int(hv[1]))
     coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
-    planes = torch.empty((planes_size(T, h, w, layout),), dtype=torch.uint8, device=dev)
+    planes = torch.empty((nplanes,), dtype=torch.uint8, device=dev)
     if out is None:
         out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
     elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
@@ -307,16 +334,19 @@ def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGE
     st = hip.stream
 
     def sync(k):
-        hip.call('mg_jpegdec_sync', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(entries),
-                 hip.ptr(bounds), hip.ptr(info), c_int(info.numel()), c_long(T), c_int(nsub), c_int(S), c_int(layout), c_int(k), st())
+        hip.call('mg_jpegdec_sync' + sfx, hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(entries),
+                 hip.ptr(bounds), hip.ptr(info), c_int(info.numel()), c_long(T), c_int(nsub), c_int(S), *geo, c_int(k), st())
 
     def output():
-        hip.call('mg_jpegdec_coef', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(first),
-                 hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(nsub), c_int(S), c_int(h), c_int(w), c_int(layout), st())
-        hip.call('mg_jpegdec_dcsum', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), c_long(T), c_int(h), c_int(w), c_int(layout), st())
-        hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
-                 c_int(h), c_int(w), c_int(layout), st())
-        if layout == L420:
+        hip.call('mg_jpegdec_coef' + sfx, hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(first),
+                 hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(nsub), c_int(S), c_int(h), c_int(w), *geo, st())
+        hip.call('mg_jpegdec_dcsum' + sfx, hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), c_long(T), c_int(h), c_int(w), *geo, st())
+        hip.call('mg_jpegdec_idct' + sfx, hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
+                 c_int(h), c_int(w), *geo, st())
+        if hv is not None:
+            hip.call('mg_jpeg_rgb_hv', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), *geo,
+                     c_int(epilogue), float3(mean), float3(std), st())
+        elif layout == L420:
             hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
         else:
             hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),

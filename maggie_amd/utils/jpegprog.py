@@ -63,6 +63,11 @@ class ProgPlan:
 
 def parse(data):
     """The marker walk of one SOF2 file's bytes -> ProgPlan. Host only; raises `Unsupported` by name for what the device does not decode."""
+    return _parse(data, jpegdec._layout)
+
+
+def _parse(data, layout_of):
+    """`parse` with the accepted samplings given, as `jpegdec._parse`."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
     d = bytes(data)
@@ -97,7 +102,7 @@ def parse(data):
                 raise Unsupported('%d-bit samples (only 8-bit progressive is decoded)' % seg[0])
             frame = dict(height=(seg[1] << 8) | seg[2], width=(seg[3] << 8) | seg[4],
                          comps=[(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(seg[5])])
-            _check_frame(frame)
+            _check_frame(frame, layout_of)
         elif m in (0xC0, 0xC1):
             raise Unsupported('SOF%d (sequential): use jpegdec for baseline files' % (m - 0xC0))
         elif 0xC3 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
@@ -199,7 +204,7 @@ def parse(data):
                     scans=scans, chains=chains)
 
 
-def _check_frame(frame):
+def _check_frame(frame, layout_of):
     comps, w, h = frame['comps'], frame['width'], frame['height']
     if len(comps) not in (1, 3):
         raise Unsupported('%d components (only YCbCr and greyscale are decoded)' % len(comps))
@@ -210,15 +215,7 @@ def _check_frame(frame):
     if len({c[0] for c in comps}) != len(comps):
         raise Unsupported('two components with one identifier')
     sampling = tuple((c[1], c[2]) for c in comps)
-    if len(comps) == 1:
-        layout = GREY
-    elif sampling == ((2, 2), (1, 1), (1, 1)):
-        layout = L420
-    elif sampling == ((1, 1), (1, 1), (1, 1)):
-        layout = L444
-    else:
-        raise Unsupported('sampling %s (only 4:2:0 and 4:4:4 are decoded)' % (sampling,))
-    frame.update(sampling=sampling, layout=layout)
+    frame.update(sampling=sampling, layout=layout_of(sampling))
 
 
 def _check_progression(scans, ncomp):
@@ -251,7 +248,8 @@ def records(plan, offset, frame, first):
     """A file's scan records int32 (scans, SCAN_WORDS) in chain order and its chain records int32 (chains, CHAIN_WORDS), with the file at `offset`
     of the buffer, for frame `frame`, its first scan record being number `first` of the launch's."""
     recs, chains = [], []
-    slots_of = {L420: ([0, 1, 2, 3], [4], [5]), L444: ([0], [1], [2]), GREY: ([0],)}[plan.layout]
+    ny = plan.sampling[0][0] * plan.sampling[0][1]             # an MCU: the luma blocks, then Cb, then Cr
+    slots_of = (list(range(ny)), [ny], [ny + 1]) if len(plan.sampling) == 3 else ([0],)
     for _, _, numbers in plan.chains:
         if not numbers:
             continue
@@ -286,10 +284,11 @@ class Decoded:
     (waves of the chain launch), `launches` (kernel launches of the call) and `readbacks`."""
 
 
-def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
+def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, hv=None):
     """The launches themselves: `blob` uint8 device tensor holding the T files, `scans` int32 (S, SCAN_WORDS) and `chains` int32 (C, CHAIN_WORDS)
     host records whose offsets point into it (`records`), `qtables` int32 (T, 3, 64). `out`: a preallocated contiguous destination of the right
-    size and dtype (else allocated). Returns a `Decoded`."""
+    size and dtype (else allocated). `hv`: the luma sampling (hs, vs) of `jpegsamp`'s layouts, which run the `_hv` entries (`layout` is then not
+    passed on). Returns a `Decoded`."""
     scans = np.ascontiguousarray(scans, np.int32).reshape(-1, SCAN_WORDS)
     chains = np.ascontiguousarray(chains, np.int32).reshape(-1, CHAIN_WORDS)
     qtables = np.ascontiguousarray(qtables, np.int32).reshape(-1, 192)
@@ -298,7 +297,7 @@ def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMA
     hip.need_cuda(blob)
     if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
         raise TypeError('blob must be a contiguous 1-D uint8 tensor')
-    if layout not in BLOCKS_PER_MCU or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+    if (hv is None and layout not in BLOCKS_PER_MCU) or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
         raise ValueError('h, w must be in 1..%d and layout one of L420, L444, GREY' % MAX_SIDE)
     if T < 1 or len(scans) < 1 or len(chains) < 1 or blob.numel() > MAX_BYTES:
         raise ValueError('at least one file, one scan and one chain, and at most %d bytes' % MAX_BYTES)
@@ -314,23 +313,34 @@ def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMA
     d_scans = torch.from_numpy(scans).to(dev, non_blocking=True)
     d_chains = torch.from_numpy(chains).to(dev, non_blocking=True)
     info = torch.zeros((T,), dtype=torch.int32, device=dev)
-    side = 16 if layout == L420 else 8
-    nblocks = ((w + side - 1) // side) * ((h + side - 1) // side) * BLOCKS_PER_MCU[layout]
+    if hv is None:
+        side = 16 if layout == L420 else 8
+        nblocks = ((w + side - 1) // side) * ((h + side - 1) // side) * BLOCKS_PER_MCU[layout]
+        nplanes = planes_size(T, h, w, layout)
+    else:
+        nblocks, per_frame = jpegdec.hv_geometry(h, w, *hv)[:2]
+        nplanes = T * per_frame
     coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
-    planes = torch.empty((planes_size(T, h, w, layout),), dtype=torch.uint8, device=dev)
+    planes = torch.empty((nplanes,), dtype=torch.uint8, device=dev)
     if out is None:
         out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
     elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
         raise ValueError('out must be a contiguous %s tensor of %d elements on %s' % ('float32' if normalize else 'uint8', T * h * w * 3, dev))
     st = hip.stream
-    launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout)
-    hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
-             c_int(h), c_int(w), c_int(layout), st())
-    if layout == L420:
-        hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
-    else:
-        hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),
+    launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout, hv)
+    if hv is not None:
+        hip.call('mg_jpegdec_idct_hv', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
+                 c_int(h), c_int(w), c_int(hv[0]), c_int(hv[1]), st())
+        hip.call('mg_jpeg_rgb_hv', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(hv[0]), c_int(hv[1]),
                  c_int(epilogue), float3(mean), float3(std), st())
+    else:
+        hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
+                 c_int(h), c_int(w), c_int(layout), st())
+        if layout == L420:
+            hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
+        else:
+            hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),
+                     c_int(epilogue), float3(mean), float3(std), st())
     host = info.cpu().numpy()
     for t in np.flatnonzero(host):
         raise ValueError('a corrupt entropy-coded segment (file %d): %s' % (t, '; '.join(v for b, v in STATUS.items() if host[t] & b)))
@@ -340,11 +350,12 @@ def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMA
     return r
 
 
-def launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout):
+def launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout, hv=None):
     """The chain launch alone (tools/jpegprog_bench.py times subsets of the chains with it): device tensors throughout."""
-    hip.call('mg_jpegprog_chains', hip.ptr(blob), c_long(blob.numel()), hip.ptr(d_scans), c_long(d_scans.shape[0]), hip.ptr(d_chains),
-             c_long(d_chains.shape[0]), hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(h), c_int(w), c_int(layout),
-             hip.stream())
+    geo = (c_int(layout),) if hv is None else (c_int(hv[0]), c_int(hv[1]))
+    hip.call('mg_jpegprog_chains' if hv is None else 'mg_jpegprog_chains_hv', hip.ptr(blob), c_long(blob.numel()), hip.ptr(d_scans),
+             c_long(d_scans.shape[0]), hip.ptr(d_chains), c_long(d_chains.shape[0]), hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T),
+             c_int(h), c_int(w), *geo, hip.stream())
 
 
 def _datas(datas):

@@ -1327,6 +1327,43 @@ int mg_matte_overlay(const uint8_t* frames_u8, const uint8_t* masks, long frames
 int mg_matte_label_ids(const void* map, int elem_bytes, long n, uint32_t* presence, void* stream);
 int mg_matte_label_planes(const void* map, int elem_bytes, long n, const uint8_t* ids, int n_ids, uint8_t* planes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Background compositing (csrc/background.hip): LoadRandomBackground -> HistogramMatching -> ComposeBackground of the reference
+ * (maggie/dataloader/transforms.py:307-370,841-864) on uint8 tensors. DESIGN.md section 32. The file is compiled without floating-point
+ * contraction; nothing reads back or synchronises, so the chain can be captured in a graph.
+ *   mg_bg_blur_crop : bg uint8 [bh][bw][3] -> out uint8 [h][w][3], the window at (x, y) of the separable integer Gaussian of the WHOLE
+ *             background: horizontal sums s1 = sum_k q_k v (16 bits, <= 255 * 256), vertical sums s2 = sum_k q_k s1 (32 bits),
+ *             out = (s2 + 32768) >> 16; border BORDER_REFLECT_101 on the background, repeated for sides below the reach. Only the window's
+ *             pixels are computed. `win` is a DEVICE int32 [MG_BG_WIN_TABLE]: [0] = ksize (odd, 1..MG_BG_MAX_KSIZE; 1 with the tap 256 is the
+ *             plain copy), [1] = x, [2] = y, [3] = 0, then ksize taps q_k >= 0 that sum to 256. The launch does not depend on the table; the
+ *             kernel clamps ksize to odd 1..25, x to 0..bw - w, y to 0..bh - h and each tap to 0..256. Needs w <= bw, h <= bh.
+ *   mg_bg_hist      : frames uint8 [pixels][3] -> counts uint32 [3][256] += the per-channel counts. The counts ACCUMULATE: the caller
+ *             zeroes them. Per-wave bins in LDS, runs of equal bytes added at once, integer atomics into the counts. pixels < 2^31.
+ *   mg_bg_match_lut : the tone curves of skimage.exposure.match_histograms (float branch) followed by the reference's blend, from the two
+ *             histograms [3][256]: luts uint8 [2][3][256], [0] the foreground's curve, [1] the background's. `draw` is a DEVICE fp32 [4]:
+ *             f32(ratio), f32(1. - ratio), match_bg (0 or 1), 0. The matched side is the foreground (match_bg 0: towards the background's
+ *             histogram) or the background; the other side and byte values that do not occur are the identity. One workgroup.
+ *   mg_bg_compose   : out[t] = uint8(clip(f64(lutF[fg]) * wt[a][0] + f64(lutB[bg]) * wt[a][1], 0, 255)), fg uint8 [frames][h][w][3], alpha
+ *             uint8 [frames][h][w], bg uint8 [bg_frames][h][w][3] with bg_frames 1 (shared) or `frames`; `luts` uint8 [2][3][256] or null
+ *             (identities); `wt` DEVICE fp64 [256][2] = a / 255.0, 1 - a / 255.0. `fg_out` [frames][h][w][3] and `bg_out` [bg_frames][h][w][3],
+ *             when given, receive lutF[fg] and lutB[bg]. A lane owns MG_MATTE_GROUP pixels at any base alignment.
+ * Each returns -2 for an argument error before any launch, -3 when the launch would exceed a grid dimension. mg_bg_limits reports the
+ * constants below to a binding that mirrors them.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_BG_MAX_KSIZE 25
+#define MG_BG_WIN_TABLE 32
+#define MG_BG_TILE_ROWS 16
+#define MG_BG_TILE_COLS 64
+#define MG_BG_THREADS 256
+#define MG_BG_MAX_SIDE 32767
+#define MG_BG_HIST_MAX_BLOCKS 2048
+int mg_bg_blur_crop(const uint8_t* bg, int bh, int bw, const int32_t* win, uint8_t* out, int h, int w, void* stream);
+int mg_bg_hist(const uint8_t* frames, long pixels, uint32_t* counts, void* stream);
+int mg_bg_match_lut(const uint32_t* hist_fg, const uint32_t* hist_bg, const float* draw, uint8_t* luts, void* stream);
+int mg_bg_compose(const uint8_t* fg, const uint8_t* alpha, const uint8_t* bg, long bg_frames, long frames, int h, int w, const uint8_t* luts,
+                  const double* wt, uint8_t* out, uint8_t* fg_out, uint8_t* bg_out, void* stream);
+int mg_bg_limits(int* max_ksize, int* win_table, int* tile_rows, int* tile_cols, int* max_side);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1078,7 +1078,16 @@ int mg_mailbox_bn_finalize_dev(const mg_mailbox* mb, const float* stats, int nre
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Baseline JPEG decoding (csrc/jpegdec.hip): the entropy-coded segments of `frames` files of one geometry -> RGB on the device. Replaces T.Load
- * (maggie/dataloader/transforms.py:38-66: Image.open(path).convert("RGB")) for SOF0 files with one interleaved scan, 4:2:0, 4:4:4 or greyscale.
+ * (maggie/dataloader/transforms.py:38-66: Image.open(path).convert("RGB")) for SOF0 files with one interleaved scan, in one of six layouts:
+ * 4:2:0, 4:4:4, greyscale, and 4:2:2, 4:4:0 and 4:1:1. csrc/jpeg_common.h maps a layout to its geometry:
+ *   luma sampling (hs, vs) = (2, 2), (1, 1), (1, 1), (2, 1), (1, 2), (4, 1) over (1, 1) Cb and Cr (greyscale: one component). An MCU is
+ *   8 hs x 8 vs pixels and holds hs * vs luma blocks (row-major) then Cb then Cr: 6, 3, 1, 4, 4, 6 blocks, the slot words 912..917 of `tabs`;
+ *   mcux = ceil(w / 8 hs), mcuy = ceil(h / 8 vs); coef int16 [frames][mcuy * mcux * blocks per MCU][64];
+ *   planes  : Y [frames][mcuy * 8 vs][yp] then Cb, Cr [frames][mcuy * 8][cp] each, `planes` 16-byte aligned. 4:2:0, 4:4:4 and greyscale are as
+ *             wide as their blocks: yp = mcux * 8 hs, cp = mcux * 8. 4:2:2, 4:4:0 and 4:1:1 are PITCHED: yp rounded up to 16, and cp too in
+ *             4:4:0: a lane of mg_jpeg_rgb_hv loads 16 luma and 8 / 16 / 4 chroma bytes at once, and a pitch of that many bytes keeps each
+ *             load inside its row and aligned. The bytes between a row's blocks and its pitch are never written and never used.
+ *             plane_bytes = frames * mcuy * 8 * (vs * yp + 2 * cp), without the 2 * cp in greyscale.
  * The Huffman decoding is the self-synchronising parallel form: the segment is cut into subsequences of `sub_bytes` raw
  * bytes, one lane each.
  *   tabs    : int32 [frames][MG_JPEGDEC_TAB_WORDS], one record per frame: four Huffman tables (DC 0, DC 1, AC 0, AC 1) of 228 words each
@@ -1094,15 +1103,22 @@ int mg_mailbox_bn_finalize_dev(const mg_mailbox* mb, const float* stats, int nre
  *   mg_jpegdec_coef  : counts -> first_block int32 [frames][nsub] (exclusive sum), then coef int16 [frames][blocks][64] (zero-filled by the
  *             caller; scan order, natural order inside a block, the DC term as its difference) and the status bits.
  *   mg_jpegdec_dcsum : DC differences -> DC terms, per component within each restart interval.
- *   mg_jpegdec_idct  : coef x table -> inverse DCT -> planes uint8: 4:2:0 in mg_jpeg_rgb's layout (finish with mg_jpeg_rgb); 4:4:4 Y, Cb, Cr
- *             [frames][h8][w8] each; greyscale Y [frames][h8][w8] (h8, w8 = h, w rounded up to 8).
+ *   mg_jpegdec_idct  : coef x table -> inverse DCT -> planes uint8: 4:2:0 in mg_jpeg_rgb's layout (finish with mg_jpeg_rgb); 4:4:4 and greyscale
+ *             finish with mg_jpegdec_rgb, the pitched layouts with mg_jpeg_rgb_hv.
  *   mg_jpegdec_rgb   : the 4:4:4 / greyscale planes -> out, the epilogues of mg_jpeg_rgb.
+ *   mg_jpeg_rgb_hv (csrc/photometric.hip): the pitched planes, named by (hs, vs) = (2, 1), (1, 2) or (4, 1), -> out with the epilogues of
+ *             mg_jpeg_rgb. Chroma is upsampled over the real ceil(h / vs) x ceil(w / hs) samples, neighbours clamped to them: 4:2:2
+ *             out[2j] = (3 c[j] + c[j-1] + 1) >> 2, out[2j+1] = (3 c[j] + c[j+1] + 2) >> 2 along the row (replication when ceil(w / 2) <= 2);
+ *             4:4:0 the same along the column at every width; 4:1:1 replication.
  * Each returns -2 for an argument error (before any launch), -3 when the launch would exceed a grid dimension. Sizes (`data_bytes`,
  * `coef_elems`, `plane_bytes`) are checked against the geometry and bound every access.
  * ------------------------------------------------------------------------------------------------------------- */
 #define MG_JPEGDEC_420 0
 #define MG_JPEGDEC_444 1
 #define MG_JPEGDEC_GREY 2
+#define MG_JPEGDEC_422 3
+#define MG_JPEGDEC_440 4
+#define MG_JPEGDEC_411 5
 #define MG_JPEGDEC_THREADS 128
 #define MG_JPEGDEC_TAB_WORDS 1120
 #define MG_JPEGDEC_MIN_SUB 8 /* 16 code bits + 11 value bits = 4 data bytes, each of which may drag a stuffed byte */
@@ -1126,10 +1142,12 @@ int mg_jpegdec_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, u
                     void* stream);
 int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int layout, int epilogue, const float* mean3,
                    const float* std3, void* stream);
+int mg_jpeg_rgb_hv(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int hs, int vs, int epilogue, const float* mean3,
+                   const float* std3, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
- * Progressive JPEG decoding (csrc/jpegprog.hip): the scans of `frames` SOF2 files of one geometry -> the coefficient buffer of mg_jpegdec_idct
- * (int16 [frames][blocks][64], zero-filled by the caller, DC terms final: mg_jpegdec_dcsum is NOT called). One wave per chain of scans
+ * Progressive JPEG decoding (csrc/jpegprog.hip): the scans of `frames` SOF2 files of one geometry, in any of mg_jpegdec's six layouts -> the
+ * coefficient buffer of mg_jpegdec_idct (int16 [frames][blocks][64], zero-filled by the caller, DC terms final: mg_jpegdec_dcsum is NOT called). One wave per chain of scans
  * (DESIGN.md section 30): a file's DC scans, or the AC scans of one of its components, in file order.
  *   scans   : int32 [nscans][MG_JPEGPROG_SCAN_WORDS], one record per scan: two Huffman tables of 228 words each (mg_jpegdec's form; a DC scan:
  *             DC table 0 and 1, an AC scan: its one table first); word 456 the segment's offset in `data`, 457 its length, 458 the restart
@@ -1151,36 +1169,6 @@ int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long fram
 int mg_jpegprog_limits(int* threads, int* scan_words, int* chain_words);
 int mg_jpegprog_chains(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
                        long coef_elems, int32_t* info, long frames, int h, int w, int layout, void* stream);
-
-/* ---------------------------------------------------------------------------------------------------------------
- * JPEG decoding of the other chroma samplings: 4:2:2, 4:4:0 and 4:1:1, that is luma sampling (hs, vs) = (2, 1), (1, 2),
- * (4, 1) over (1, 1) Cb and Cr. Each entry is its namesake above with `int hs, int vs` where that one takes `int layout`, runs the same kernels,
- * and takes the same buffers; the entries above keep refusing every layout but their three. What differs is the geometry:
- *   an MCU is 8 hs x 8 vs pixels and holds hs * vs luma blocks (row-major) then Cb then Cr: 4, 4, 6 blocks, the slot words 912..917 of `tabs`;
- *   mcux = ceil(w / 8 hs), mcuy = ceil(h / 8 vs); coef int16 [frames][mcuy * mcux * (hs * vs + 2)][64];
- *   planes  : Y [frames][mcuy * 8 vs][yp] then Cb, Cr [frames][mcuy * 8][cp] each, with the row pitches yp = mcux * 8 hs rounded up to 16 and
- *             cp = mcux * 8, in 4:4:0 rounded up to 16: a lane of mg_jpeg_rgb_hv loads 16 luma and 8 / 16 / 4 chroma bytes at once, and a pitch
- *             of that many bytes keeps each load inside its row and aligned. The bytes between a row's blocks and its pitch are never written
- *             and never used. plane_bytes = frames * mcuy * 8 * (vs * yp + 2 * cp); `planes` 16-byte aligned.
- *   mg_jpeg_rgb_hv (csrc/photometric.hip): the planes -> out with the epilogues of mg_jpeg_rgb. Chroma is upsampled over the real
- *             ceil(h / vs) x ceil(w / hs) samples, neighbours clamped to them: 4:2:2 out[2j] = (3 c[j] + c[j-1] + 1) >> 2, out[2j+1] =
- *             (3 c[j] + c[j+1] + 2) >> 2 along the row (replication when ceil(w / 2) <= 2); 4:4:0 the same along the column at every width;
- *             4:1:1 replication.
- * Each returns -2 for any other (hs, vs) and for every bad size or buffer (before any launch), -3 when the launch would exceed a grid dimension.
- * ------------------------------------------------------------------------------------------------------------- */
-int mg_jpegdec_sync_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts,
-                       unsigned long long* entries, unsigned long long* bounds, int32_t* info, int info_words, long frames, int nsub, int sub_bytes,
-                       int hs, int vs, int launch, void* stream);
-int mg_jpegdec_coef_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
-                       int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h, int w, int hs,
-                       int vs, void* stream);
-int mg_jpegdec_dcsum_hv(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int hs, int vs, void* stream);
-int mg_jpegdec_idct_hv(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h, int w, int hs,
-                       int vs, void* stream);
-int mg_jpeg_rgb_hv(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int hs, int vs, int epilogue, const float* mean3,
-                   const float* std3, void* stream);
-int mg_jpegprog_chains_hv(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
-                          long coef_elems, int32_t* info, long frames, int h, int w, int hs, int vs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * PNG decoding (csrc/pngdec.hip): the zlib streams (concatenated IDAT payloads) of `planes` non-interlaced files of one size -> the L plane of

@@ -1,7 +1,8 @@
-// Baseline JPEG decoding on the device: the entropy-coded segment of T files of one geometry -> coefficients -> component planes -> RGB. The
-//   lossy half (dequantisation, JDCT_ISLOW inverse transform, upsampling, YCbCr -> RGB) is photometric.hip's, pinned to Pillow (DESIGN.md
-//   section 19); this file adds the Huffman decoding in the self-synchronising parallel form of Weissenberger and Schmidt and
-//   restates the inverse passes for blocks that arrive as coefficients.
+// Baseline JPEG decoding on the device: the entropy-coded segment of T files of one geometry, in any of the six layouts of include/maggie_hip.h
+//   (jpeg_common.h maps a layout to its geometry) -> coefficients -> component planes -> RGB. The lossy half (dequantisation, JDCT_ISLOW inverse
+//   transform, upsampling, YCbCr -> RGB) is photometric.hip's, pinned to Pillow; this file adds the Huffman decoding in
+//   the self-synchronising parallel form of Weissenberger and Schmidt and runs jpeg_common.h's inverse passes on blocks that arrive
+//   as coefficients (DESIGN.md sections 25, 31 and 33).
 //
 // A frame's segment is cut into subsequences of `sub_bytes` raw bytes; one lane owns one subsequence. A lane's state is (bit position, block
 //   slot within the MCU, zig-zag index); the number of blocks it completed is kept next to it. Bit positions count RAW bits: a stuffed 0x00
@@ -18,7 +19,8 @@
 //   entries, writing int16 coefficients de-zig-zagged into zero-filled blocks in scan order, the DC term as its DIFFERENCE; status bits.
 // jd_dcsum_kernel  per frame and component: the segmented (per restart interval) inclusive sum that turns differences into DC terms.
 // jd_idct_kernel   coefficient x table, columns (descale 11), rows (descale 18), + 128, range limit; one lane per 8-point pass on [8][9]-pitch
-//   LDS blocks; writes the plane layout mg_jpeg_rgb reads.  jd_rgb_kernel 4:4:4 and greyscale planes -> raw bytes or the Normalize epilogue.
+//   LDS blocks; writes the plane layout mg_jpeg_rgb (4:2:0), jd_rgb_kernel or mg_jpeg_rgb_hv (4:2:2, 4:4:0, 4:1:1: pitched planes) reads.
+// jd_rgb_kernel    4:4:4 and greyscale planes -> raw bytes or the Normalize epilogue.
 #ifndef MG_HOST_EMU
 #include "common.h"
 #include "../../include/maggie_hip.h"
@@ -27,70 +29,29 @@
 #endif
 
 namespace {
+#include "jpeg_common.h"
 
 constexpr int NT = MG_JPEGDEC_THREADS;                                     // lanes = subsequences per workgroup of the decode kernels
 constexpr int TW = MG_JPEGDEC_TAB_WORDS;                                   // int32 words of a frame's record
-constexpr int HT = 228;                                                    // words of one Huffman table: look[256] u16, maxcode[18], valoff[18], vals[256] u8
 constexpr int W_SLOT = 4 * HT, W_OFF = W_SLOT + 6, W_LEN = W_OFF + 1, W_RI = W_OFF + 2, W_QT = 928;
 constexpr int PT = 256;                                                    // lanes of the other kernels
 constexpr int RP = 9, BP = 8 * RP;                                         // row and block pitch in dwords (photometric.hip's)
 constexpr unsigned long long INVALID = ~0ull;
 static_assert(W_QT + 192 == TW && NT % 64 == 0 && NT <= PT, "record layout");
 
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373, F_1_175875602 = 9633;
-constexpr int F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995;
-constexpr int F_3_072711026 = 25172;
-
-MG_DEVCONST uint8_t NATURAL[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// jpeg_idct_islow's pass on dequantised values (photometric.hip's idct8, verbatim)
-template <int N>
-__device__ __forceinline__ void idct8(int (&d)[8]) {
-    int z1 = (d[2] + d[6]) * F_0_541196100;
-    int tmp2 = z1 + d[6] * (-F_1_847759065), tmp3 = z1 + d[2] * F_0_765366865;
-    int tmp0 = (d[0] + d[4]) * 8192, tmp1 = (d[0] - d[4]) * 8192;
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    tmp0 = d[7]; tmp1 = d[5]; tmp2 = d[3]; tmp3 = d[1];
-    z1 = tmp0 + tmp3;
-    int z2 = tmp1 + tmp2, z3 = tmp0 + tmp2, z4 = tmp1 + tmp3;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    tmp0 *= F_0_298631336; tmp1 *= F_2_053119869; tmp2 *= F_3_072711026; tmp3 *= F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447; z3 *= -F_1_961570560; z4 *= -F_0_390180644;
-    z3 += z5; z4 += z5;
-    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-    d[0] = descale(tmp10 + tmp3, N); d[7] = descale(tmp10 - tmp3, N);
-    d[1] = descale(tmp11 + tmp2, N); d[6] = descale(tmp11 - tmp2, N);
-    d[2] = descale(tmp12 + tmp1, N); d[5] = descale(tmp12 - tmp1, N);
-    d[3] = descale(tmp13 + tmp0, N); d[4] = descale(tmp13 - tmp0, N);
-}
-
-// libjpeg's range-limit table behind the inverse transform, indexed with the descaled value masked to 10 bits: v + 128 for -128 <= v < 128,
-// 255 up to 511, 0 from -512 on -- and, unlike a clamp, periodic beyond
-__device__ __forceinline__ int range_limit(int v) {
-    const int i = v & 1023;
-    return i < 128 ? i + 128 : (i < 512 ? 255 : (i < 896 ? 0 : i - 896));
-}
+MG_DEVCONST uint8_t NATURAL[64] = MG_JPEG_ZIGZAG;
 
 // blocks per MCU, the MCU grid, luma blocks per MCU row and column, the row pitch of the luma plane and of a chroma plane in bytes
 struct Geo { int bpm, mcux, mcuy, hs, vs, yp, cp; };
-// luma sampling (hs, vs) over (1, 1) chroma (`ncomp` 3), or one component. The 4:2:0 / 4:4:4 / grey planes are as wide as their blocks; the
-// planes of mg_jpeg_rgb_hv are pitched so that a lane's widest load stays inside its row: luma to 16 bytes, 4:4:0 chroma (16 samples a lane) too
-__host__ __device__ __forceinline__ Geo geo_hv(int hs, int vs, int ncomp, int h, int w, bool pitched) {
-    Geo g;
-    g.hs = hs; g.vs = vs;
-    g.bpm = ncomp == 1 ? 1 : hs * vs + 2;
-    g.mcux = (w + 8 * hs - 1) / (8 * hs);
-    g.mcuy = (h + 8 * vs - 1) / (8 * vs);
-    g.yp = g.mcux * 8 * hs; g.cp = g.mcux * 8;
-    if (pitched) { g.yp = (g.yp + 15) & ~15; if (vs == 2) g.cp = (g.cp + 15) & ~15; }
-    return g;
+// the struct of a layout and the bytes of its planes (jpeg_common.h); bad_layout: anything but the six
+bool bad_layout(int layout) { JpegLayout l; return !jpeg_layout(layout, 8, 8, l); }
+Geo geo_of(int layout, int h, int w) {
+    JpegLayout l = {};
+    jpeg_layout(layout, h, w, l);
+    return Geo{l.bpm, l.mcux, l.mcuy, l.hs, l.vs, l.yp, l.cp};
 }
-__host__ __device__ __forceinline__ Geo geo_of(int layout, int h, int w) {
-    const int hs = layout == MG_JPEGDEC_420 ? 2 : 1;
-    return geo_hv(hs, hs, layout == MG_JPEGDEC_GREY ? 1 : 3, h, w, false);
+long plane_bytes_of(long frames, int layout, const Geo& g) {
+    return frames * (long)g.mcuy * 8 * ((long)g.vs * g.yp + (layout == MG_JPEGDEC_GREY ? 0L : 2L) * g.cp);
 }
 
 // ---- the bit reader and one subsequence ------------------------------------------------------------------------------------------------------
@@ -159,9 +120,9 @@ __device__ __forceinline__ unsigned long long run_sub(unsigned long long st, lon
         else {
             for (int l = 9; l <= 16; ++l) {
                 const int code = (int)(bits >> (32 - l));
-                if (code <= tb[128 + l]) {
-                    const int idx = tb[146 + l] + code;
-                    if ((unsigned)idx < 256u) { len_c = l; sym = ((const uint8_t*)(tb + 164))[idx]; }
+                if (code <= tb[HT_MAXCODE + l]) {
+                    const int idx = tb[HT_VALOFF + l] + code;
+                    if ((unsigned)idx < 256u) { len_c = l; sym = ((const uint8_t*)(tb + HT_VALS))[idx]; }
                     break;
                 }
             }
@@ -426,19 +387,11 @@ __global__ __launch_bounds__(PT) void jd_rgb_kernel(const uint8_t* __restrict__ 
     }
 }
 
-bool bad_layout(int layout) { return layout != MG_JPEGDEC_420 && layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY; }
-bool bad_size(long frames, int h, int w) { return frames < 0 || h <= 0 || w <= 0 || h > MG_JPEG_MAX_SIDE || w > MG_JPEG_MAX_SIDE; }
 bool bad_sub(int nsub, int sub_bytes) {
     return nsub <= 0 || sub_bytes < MG_JPEGDEC_MIN_SUB || sub_bytes > MG_JPEGDEC_MAX_SUB || (long)nsub * sub_bytes > MG_JPEGDEC_MAX_BYTES;
 }
-long plane_bytes_of(long frames, int layout, const Geo& g) {
-    const long luma = (long)g.mcux * g.mcuy * 64 * g.hs * g.hs;
-    return frames * (layout == MG_JPEGDEC_GREY ? luma : (layout == MG_JPEGDEC_444 ? 3 * luma : luma + luma / 2));
-}
-bool bad_hv(int hs, int vs) { return !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1)); }
-long plane_bytes_hv(long frames, const Geo& g) { return frames * (long)g.mcuy * 8 * ((long)g.vs * g.yp + 2L * g.cp); }
 
-// the launches behind the entry points, the geometry given: the layout entries and the (hs, vs) entries share them
+// the launches behind the entry points, the geometry given
 int launch_sync(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts, unsigned long long* entries,
                 unsigned long long* bounds, int32_t* info, long frames, int nsub, int sub_bytes, int bpm, int launch, void* stream) {
     if (!data || !tabs || !exits || !counts || !entries || !bounds || !info) return -2;
@@ -508,57 +461,28 @@ extern "C" int mg_jpegdec_sync(const uint8_t* data, long data_bytes, const int32
     return launch_sync(data, data_bytes, tabs, exits, counts, entries, bounds, info, frames, nsub, sub_bytes, geo_of(layout, 8, 8).bpm, launch, stream);
 }
 
-extern "C" int mg_jpegdec_sync_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, unsigned long long* exits, int32_t* counts,
-                                  unsigned long long* entries, unsigned long long* bounds, int32_t* info, int info_words, long frames, int nsub,
-                                  int sub_bytes, int hs, int vs, int launch, void* stream) {
-    if (frames < 0 || bad_hv(hs, vs) || bad_sub(nsub, sub_bytes) || data_bytes < 0 || launch < 0 || info_words < 4 ||
-        launch > (info_words - 4) / 2) return -2;
-    if (frames == 0) return 0;
-    return launch_sync(data, data_bytes, tabs, exits, counts, entries, bounds, info, frames, nsub, sub_bytes, hs * vs + 2, launch, stream);
-}
-
 extern "C" int mg_jpegdec_coef(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
                                int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h, int w,
                                int layout, void* stream) {
-    if (bad_size(frames, h, w) || bad_layout(layout) || bad_sub(nsub, sub_bytes) || data_bytes < 0) return -2;
+    if (jpeg_bad_size(frames, h, w) || bad_layout(layout) || bad_sub(nsub, sub_bytes) || data_bytes < 0) return -2;
     return launch_coef(data, data_bytes, tabs, exits, counts, first_block, coef, coef_elems, info, frames, nsub, sub_bytes, geo_of(layout, h, w), stream);
 }
 
-extern "C" int mg_jpegdec_coef_hv(const uint8_t* data, long data_bytes, const int32_t* tabs, const unsigned long long* exits, const int32_t* counts,
-                                  int32_t* first_block, int16_t* coef, long coef_elems, int32_t* info, long frames, int nsub, int sub_bytes, int h,
-                                  int w, int hs, int vs, void* stream) {
-    if (bad_size(frames, h, w) || bad_hv(hs, vs) || bad_sub(nsub, sub_bytes) || data_bytes < 0) return -2;
-    return launch_coef(data, data_bytes, tabs, exits, counts, first_block, coef, coef_elems, info, frames, nsub, sub_bytes,
-                       geo_hv(hs, vs, 3, h, w, true), stream);
-}
-
 extern "C" int mg_jpegdec_dcsum(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int layout, void* stream) {
-    if (bad_size(frames, h, w) || bad_layout(layout)) return -2;
+    if (jpeg_bad_size(frames, h, w) || bad_layout(layout)) return -2;
     return launch_dcsum(coef, coef_elems, tabs, frames, geo_of(layout, h, w), stream);
-}
-
-extern "C" int mg_jpegdec_dcsum_hv(int16_t* coef, long coef_elems, const int32_t* tabs, long frames, int h, int w, int hs, int vs, void* stream) {
-    if (bad_size(frames, h, w) || bad_hv(hs, vs)) return -2;
-    return launch_dcsum(coef, coef_elems, tabs, frames, geo_hv(hs, vs, 3, h, w, true), stream);
 }
 
 extern "C" int mg_jpegdec_idct(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h, int w,
                                int layout, void* stream) {
-    if (bad_size(frames, h, w) || bad_layout(layout)) return -2;
+    if (jpeg_bad_size(frames, h, w) || bad_layout(layout)) return -2;
     const Geo g = geo_of(layout, h, w);
     return launch_idct(coef, coef_elems, tabs, planes, plane_bytes, plane_bytes_of(frames, layout, g), frames, g, stream);
 }
 
-extern "C" int mg_jpegdec_idct_hv(const int16_t* coef, long coef_elems, const int32_t* tabs, uint8_t* planes, long plane_bytes, long frames, int h,
-                                  int w, int hs, int vs, void* stream) {
-    if (bad_size(frames, h, w) || bad_hv(hs, vs)) return -2;
-    const Geo g = geo_hv(hs, vs, 3, h, w, true);
-    return launch_idct(coef, coef_elems, tabs, planes, plane_bytes, plane_bytes_hv(frames, g), frames, g, stream);
-}
-
 extern "C" int mg_jpegdec_rgb(const uint8_t* planes, long plane_bytes, void* out, long frames, int h, int w, int layout, int epilogue,
                               const float* mean3, const float* std3, void* stream) {
-    if (bad_size(frames, h, w) || (layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY) || (epilogue != MG_PHOTO_RAW && epilogue != MG_PHOTO_NORM) ||
+    if (jpeg_bad_size(frames, h, w) || (layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY) || (epilogue != MG_PHOTO_RAW && epilogue != MG_PHOTO_NORM) ||
         !mean3 || !std3) return -2;
     const Geo g = geo_of(layout, h, w);
     if (plane_bytes != plane_bytes_of(frames, layout, g)) return -2;

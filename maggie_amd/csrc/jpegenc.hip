@@ -26,8 +26,9 @@
 #endif
 
 namespace {
+#include "jpeg_common.h"
 
-// ---- the transform half: photometric.hip's, restated --------------------------------------------------------------------------------------------
+// ---- the transform half: photometric.hip's tiles, jpeg_common.h's passes ----------------------------------------------------------------------
 constexpr int TH = MG_JPEG_TILE_ROWS, TW = MG_JPEG_TILE_COLS;
 constexpr int NYB = (TH / 8) * (TW / 8), NCB = (TH / 16) * (TW / 16);
 constexpr int NB = NYB + 2 * NCB;
@@ -35,35 +36,7 @@ constexpr int NT = MG_JPEG_THREADS;
 constexpr int RP = 9, BP = 8 * RP;
 static_assert(TH == 32 && TW == 64 && NT == NB * 8 && NT % 64 == 0, "384 lanes: 48 blocks of 8 lines");
 
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373, F_1_175875602 = 9633;
-constexpr int F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995;
-constexpr int F_3_072711026 = 25172;
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 __device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
-
-template <bool FIRST>
-__device__ __forceinline__ void fdct8(int (&d)[8]) {
-    const int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7], tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
-    const int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5], tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    constexpr int n = FIRST ? 11 : 15;
-    d[0] = FIRST ? (tmp10 + tmp11) * 4 : descale(tmp10 + tmp11, 2);
-    d[4] = FIRST ? (tmp10 - tmp11) * 4 : descale(tmp10 - tmp11, 2);
-    int z1 = (tmp12 + tmp13) * F_0_541196100;
-    d[2] = descale(z1 + tmp13 * F_0_765366865, n);
-    d[6] = descale(z1 + tmp12 * (-F_1_847759065), n);
-    z1 = tmp4 + tmp7;
-    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    const int t4 = tmp4 * F_0_298631336, t5 = tmp5 * F_2_053119869, t6 = tmp6 * F_3_072711026, t7 = tmp7 * F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447; z3 *= -F_1_961570560; z4 *= -F_0_390180644;
-    z3 += z5; z4 += z5;
-    d[7] = descale(t4 + z1 + z3, n);
-    d[5] = descale(t5 + z2 + z4, n);
-    d[3] = descale(t6 + z2 + z3, n);
-    d[1] = descale(t7 + z1 + z4, n);
-}
 
 __global__ __launch_bounds__(NT) void je_coef_kernel(const uint8_t* __restrict__ in, const uint8_t* __restrict__ lut, const int16_t* __restrict__ noise,
                                                      int nc, const int32_t* __restrict__ qtab, int16_t* __restrict__ coef, int h, int w, int mx,
@@ -220,8 +193,7 @@ static_assert(T_AC_C.e[0x00] == (0x0u | (2u << 16)) && T_AC_C.e[0xF0] == (0x3FAu
 // DC luma, AC luma, DC chroma, AC chroma: 4 x 256 words
 __device__ const HuffTab JE_TABS[4] = {T_DC_L, T_AC_L, T_DC_C, T_AC_C};
 
-__device__ const uint8_t JE_ZIGZAG[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__device__ const uint8_t JE_ZIGZAG[64] = MG_JPEG_ZIGZAG;
 
 constexpr int ET = MG_JPEGENC_THREADS;                                     // the entropy kernels: four waves
 constexpr int PBK = MG_JPEGENC_PACK_BLOCKS;                                // blocks of a packing workgroup

@@ -1,4 +1,4 @@
-// Progressive JPEG decoding on the device: the scans of T SOF2 files of one geometry -> the coefficient buffer of jpegdec.hip (int16
+// Progressive JPEG decoding on the device: the scans of T SOF2 files of one geometry, in any of jpegdec.hip's six layouts -> its coefficient buffer (int16
 //   [frames][blocks][64], natural order, interleaved MCU order with the padding blocks, DC terms final). Everything behind the coefficients is
 //   jpegdec.hip's (mg_jpegdec_idct and the colour kernels), unchanged.
 //
@@ -18,7 +18,7 @@
 //   An AC chain never stores coefficient 0 and the DC chain stores nothing else, and every store is one int16, so all chains of all files share
 //   one launch. No wave waits for another. Every loop runs under a bound from the sizes passed in (blocks, 64 symbols per block, four bytes per
 //   refill); a corrupt stream sets a status bit in info[frame] and ends the chain.
-// The scan's Huffman words (two tables of jpegdec's 228 words) and a window of the segment's bytes live in LDS. The reader skips a stuffed 0x00
+// The scan's Huffman words (two tables of jpeg_common.h's HT words) and a window of the segment's bytes live in LDS. The reader skips a stuffed 0x00
 //   behind a data 0xFF and stops in front of any marker; a restart realigns to the byte, checks RSTn's number and resets the predictors and
 //   the end-of-band run.
 #ifndef MG_HOST_EMU
@@ -33,10 +33,10 @@ __device__ __forceinline__ unsigned long long jp_ballot(int p) { return __ballot
 #endif
 
 namespace {
+#include "jpeg_common.h"
 
 constexpr int NL = MG_JPEGPROG_THREADS;                                    // lanes of a chain's wave
 constexpr int SW = MG_JPEGPROG_SCAN_WORDS, CW = MG_JPEGPROG_CHAIN_WORDS;
-constexpr int HT = 228;                                                    // words of one Huffman table (jpegdec.hip's)
 constexpr int S_OFF = 2 * HT, S_LEN = S_OFF + 1, S_RI = S_OFF + 2, S_SS = S_OFF + 3, S_SE = S_OFF + 4, S_AH = S_OFF + 5, S_AL = S_OFF + 6;
 constexpr int S_NSLOT = S_OFF + 7, S_COMP = S_OFF + 8, S_SLOT = S_OFF + 10, HDR = 24;
 constexpr int AHEAD = 16;                                                  // blocks a refinement scan reads ahead
@@ -44,8 +44,7 @@ constexpr int WIN = 2048;                                                  // by
 constexpr int STOP_NONE = 0, STOP_RST = 1, STOP_END = 2;
 static_assert(NL == 64 && S_OFF + HDR == SW && S_SLOT + 6 <= SW, "record layout");
 
-MG_DEVCONST uint8_t JP_NATURAL[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                                      35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+MG_DEVCONST uint8_t JP_NATURAL[64] = MG_JPEG_ZIGZAG;
 
 // ---- the bit reader: wave-uniform, its bytes through an LDS window ------------------------------------------------------------------------------
 struct Bits {
@@ -138,9 +137,9 @@ __device__ __forceinline__ int jp_symbol(Bits& r, const int* tb, int& status) {
     else {
         for (int l = 9; l <= 16; ++l) {
             const int code = (int)(peek >> (16 - l));
-            if (code <= JP_UNI(tb[128 + l])) {
-                const int idx = JP_UNI(tb[146 + l]) + code;
-                if ((unsigned)idx < 256u) { len_c = l; sym = JP_UNI(((const uint8_t*)(tb + 164))[idx]); }
+            if (code <= JP_UNI(tb[HT_MAXCODE + l])) {
+                const int idx = JP_UNI(tb[HT_VALOFF + l]) + code;
+                if ((unsigned)idx < 256u) { len_c = l; sym = JP_UNI(((const uint8_t*)(tb + HT_VALS))[idx]); }
                 break;
             }
         }
@@ -168,16 +167,14 @@ __device__ __forceinline__ void jp_restart(Bits& r, int done, int& status) {
 }
 
 struct Geo { int bpm, mcux, mcuy, ncomp, hl, vl; };                        // hl, vl: log2 of the luma blocks per MCU row and column
-// luma sampling (hs, vs), each 1, 2 or 4, over (1, 1) chroma, or one component
-__host__ __device__ __forceinline__ Geo jp_geo(int hs, int vs, int ncomp, int h, int w) {
-    Geo g;
-    g.bpm = ncomp == 1 ? 1 : hs * vs + 2;
-    g.ncomp = ncomp;
-    g.hl = hs == 4 ? 2 : hs - 1;
-    g.vl = vs == 4 ? 2 : vs - 1;
-    g.mcux = (w + 8 * hs - 1) / (8 * hs);
-    g.mcuy = (h + 8 * vs - 1) / (8 * vs);
-    return g;
+// the struct of a layout (jpeg_common.h); false for anything but the six
+bool jp_geo(int layout, int h, int w, Geo& g) {
+    JpegLayout l;
+    if (!jpeg_layout(layout, h, w, l)) return false;
+    g.bpm = l.bpm; g.mcux = l.mcux; g.mcuy = l.mcuy; g.ncomp = l.ncomp;
+    g.hl = l.hs == 4 ? 2 : l.hs - 1;
+    g.vl = l.vs == 4 ? 2 : l.vs - 1;
+    return true;
 }
 
 // block (by, bx) of component `comp`, counted over the component's real blocks -> its index in the MCU-major buffer: a luma block lives in MCU
@@ -370,24 +367,6 @@ __global__ __launch_bounds__(NL) void jp_chain_kernel(const uint8_t* __restrict_
     if (status && threadIdx.x == 0) atomicOr(&info[t], status);
 }
 
-// the launch behind both entry points, the geometry given
-int jp_launch(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains, int16_t* coef,
-              long coef_elems, int32_t* info, long frames, int h, int w, const Geo& g, void* stream) {
-    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
-    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
-    if (frames == 0 || nchains == 0) return 0;
-    if (!data || !scans || !chains || !coef || !info) return -2;
-    if (nchains > 0x7fffffffL) return -3;
-    hipLaunchKernelGGL(jp_chain_kernel, dim3((unsigned)nchains), dim3(NL), 0, (hipStream_t)stream, data, data_bytes, scans, nscans, chains, coef, info,
-                       frames, h, w, g);
-    MG_CHECK_LAUNCH();
-    return 0;
-}
-bool jp_bad(long data_bytes, long nscans, long nchains, long frames, int h, int w) {
-    return frames < 0 || h <= 0 || w <= 0 || h > MG_JPEG_MAX_SIDE || w > MG_JPEG_MAX_SIDE || data_bytes < 0 || data_bytes > MG_JPEGDEC_MAX_BYTES ||
-           nscans < 0 || nchains < 0;
-}
-
 }  // namespace
 
 extern "C" int mg_jpegprog_limits(int* threads, int* scan_words, int* chain_words) {
@@ -398,14 +377,16 @@ extern "C" int mg_jpegprog_limits(int* threads, int* scan_words, int* chain_word
 
 extern "C" int mg_jpegprog_chains(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains,
                                   int16_t* coef, long coef_elems, int32_t* info, long frames, int h, int w, int layout, void* stream) {
-    if (jp_bad(data_bytes, nscans, nchains, frames, h, w) || (layout != MG_JPEGDEC_420 && layout != MG_JPEGDEC_444 && layout != MG_JPEGDEC_GREY)) return -2;
-    const int hs = layout == MG_JPEGDEC_420 ? 2 : 1;
-    return jp_launch(data, data_bytes, scans, nscans, chains, nchains, coef, coef_elems, info, frames, h, w,
-                     jp_geo(hs, hs, layout == MG_JPEGDEC_GREY ? 1 : 3, h, w), stream);
-}
-
-extern "C" int mg_jpegprog_chains_hv(const uint8_t* data, long data_bytes, const int32_t* scans, long nscans, const int32_t* chains, long nchains,
-                                     int16_t* coef, long coef_elems, int32_t* info, long frames, int h, int w, int hs, int vs, void* stream) {
-    if (jp_bad(data_bytes, nscans, nchains, frames, h, w) || !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1))) return -2;
-    return jp_launch(data, data_bytes, scans, nscans, chains, nchains, coef, coef_elems, info, frames, h, w, jp_geo(hs, vs, 3, h, w), stream);
+    Geo g;
+    if (jpeg_bad_size(frames, h, w) || data_bytes < 0 || data_bytes > MG_JPEGDEC_MAX_BYTES || nscans < 0 || nchains < 0 || !jp_geo(layout, h, w, g))
+        return -2;
+    const long nbf = (long)g.mcux * g.mcuy * g.bpm;
+    if (nbf > 0x7fffffffL / 64 || coef_elems != frames * nbf * 64) return -2;
+    if (frames == 0 || nchains == 0) return 0;
+    if (!data || !scans || !chains || !coef || !info) return -2;
+    if (nchains > 0x7fffffffL) return -3;
+    hipLaunchKernelGGL(jp_chain_kernel, dim3((unsigned)nchains), dim3(NL), 0, (hipStream_t)stream, data, data_bytes, scans, nscans, chains, coef, info,
+                       frames, h, w, g);
+    MG_CHECK_LAUNCH();
+    return 0;
 }

@@ -19,7 +19,7 @@
 //   ceil(h / 2) x ceil(w / 2) samples (neighbours clamped to them, never the padding), 2 x 2 replication when ceil(w / 2) <= 2, YCbCr -> RGB, clamp;
 //   three uint4 of raw bytes, or four float4 per channel plane with the Normalize epilogue of pixel_norm.h; per element on ragged widths and
 //   unaligned bases.
-// jpeg_rgb_hv_kernel the same for the planes mg_jpegdec_idct_hv leaves (luma sampling (2,1), (1,2) or (4,1) over (1,1) chroma, DESIGN.md section
+// jpeg_rgb_hv_kernel the same for the planes mg_jpegdec_idct leaves (luma sampling (2,1), (1,2) or (4,1) over (1,1) chroma, DESIGN.md section
 //   31): 16 luma bytes and 8 / 2 x 16 / 4 chroma bytes per lane in one load each; 4:2:2 the triangle filter along the row (replication when
 //   ceil(w / 2) <= 2), 4:4:0 along the column at every width, 4:1:1 replication; neighbours clamped to the real samples.
 // photo_point_kernel the tone curve and / or the saturating add alone, the same 16 pixels per lane and the same two epilogues.
@@ -30,6 +30,7 @@
 #endif
 
 namespace {
+#include "jpeg_common.h"
 
 constexpr int TH = MG_JPEG_TILE_ROWS, TW = MG_JPEG_TILE_COLS;
 constexpr int NYB = (TH / 8) * (TW / 8), NCB = (TH / 16) * (TW / 16);      // luma blocks, chroma blocks per component
@@ -39,58 +40,7 @@ constexpr int RP = 9, BP = 8 * RP;                                         // ro
 constexpr int PT = 256;                                                    // the pointwise kernels
 static_assert(TH == 32 && TW == 64 && NT == NB * 8 && NT % 64 == 0, "384 lanes: 48 blocks of 8 lines");
 
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270, F_0_899976223 = 7373, F_1_175875602 = 9633;
-constexpr int F_1_501321110 = 12299, F_1_847759065 = 15137, F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995;
-constexpr int F_3_072711026 = 25172;
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 __device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
-
-// one pass of jpeg_fdct_islow (CONST_BITS 13, PASS1_BITS 2): FIRST = the row pass (outputs 0 and 4 times 4, the others descaled by 11), else the
-// column pass (2 and 15)
-template <bool FIRST>
-__device__ __forceinline__ void fdct8(int (&d)[8]) {
-    const int tmp0 = d[0] + d[7], tmp7 = d[0] - d[7], tmp1 = d[1] + d[6], tmp6 = d[1] - d[6];
-    const int tmp2 = d[2] + d[5], tmp5 = d[2] - d[5], tmp3 = d[3] + d[4], tmp4 = d[3] - d[4];
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    constexpr int n = FIRST ? 11 : 15;
-    d[0] = FIRST ? (tmp10 + tmp11) * 4 : descale(tmp10 + tmp11, 2);
-    d[4] = FIRST ? (tmp10 - tmp11) * 4 : descale(tmp10 - tmp11, 2);
-    int z1 = (tmp12 + tmp13) * F_0_541196100;
-    d[2] = descale(z1 + tmp13 * F_0_765366865, n);
-    d[6] = descale(z1 + tmp12 * (-F_1_847759065), n);
-    z1 = tmp4 + tmp7;
-    int z2 = tmp5 + tmp6, z3 = tmp4 + tmp6, z4 = tmp5 + tmp7;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    const int t4 = tmp4 * F_0_298631336, t5 = tmp5 * F_2_053119869, t6 = tmp6 * F_3_072711026, t7 = tmp7 * F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447; z3 *= -F_1_961570560; z4 *= -F_0_390180644;
-    z3 += z5; z4 += z5;
-    d[7] = descale(t4 + z1 + z3, n);
-    d[5] = descale(t5 + z2 + z4, n);
-    d[3] = descale(t6 + z2 + z3, n);
-    d[1] = descale(t7 + z1 + z4, n);
-}
-
-// one pass of jpeg_idct_islow on dequantised values, descaled by N bits (11 for the columns, 18 for the rows)
-template <int N>
-__device__ __forceinline__ void idct8(int (&d)[8]) {
-    int z1 = (d[2] + d[6]) * F_0_541196100;
-    int tmp2 = z1 + d[6] * (-F_1_847759065), tmp3 = z1 + d[2] * F_0_765366865;
-    int tmp0 = (d[0] + d[4]) * 8192, tmp1 = (d[0] - d[4]) * 8192;
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-    tmp0 = d[7]; tmp1 = d[5]; tmp2 = d[3]; tmp3 = d[1];
-    z1 = tmp0 + tmp3;
-    int z2 = tmp1 + tmp2, z3 = tmp0 + tmp2, z4 = tmp1 + tmp3;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    tmp0 *= F_0_298631336; tmp1 *= F_2_053119869; tmp2 *= F_3_072711026; tmp3 *= F_1_501321110;
-    z1 *= -F_0_899976223; z2 *= -F_2_562915447; z3 *= -F_1_961570560; z4 *= -F_0_390180644;
-    z3 += z5; z4 += z5;
-    tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-    d[0] = descale(tmp10 + tmp3, N); d[7] = descale(tmp10 - tmp3, N);
-    d[1] = descale(tmp11 + tmp2, N); d[6] = descale(tmp11 - tmp2, N);
-    d[2] = descale(tmp12 + tmp1, N); d[5] = descale(tmp12 - tmp1, N);
-    d[3] = descale(tmp13 + tmp0, N); d[4] = descale(tmp13 - tmp0, N);
-}
 
 __global__ __launch_bounds__(NT) void jpeg_ycc_kernel(const uint8_t* __restrict__ in, uint8_t* __restrict__ planes, const uint8_t* __restrict__ lut,
                                                       const int16_t* __restrict__ noise, int nc, const int32_t* __restrict__ qtab, long frames,
@@ -294,7 +244,7 @@ __global__ __launch_bounds__(PT) void jpeg_rgb_kernel(const uint8_t* __restrict_
     store16<EPI>(px, out, t, y, x0, n, h, w, vec, mean, std);
 }
 
-// planes as mg_jpegdec_idct_hv leaves them: Y [T][ph][yp], Cb and Cr [T][chh][cp]; yp is a multiple of 16 and cp of the chroma bytes a lane loads,
+// planes as mg_jpegdec_idct leaves them: Y [T][ph][yp], Cb and Cr [T][chh][cp]; yp is a multiple of 16 and cp of the chroma bytes a lane loads,
 // so that every load below lies inside its row and is aligned to its own size
 template <int EPI, int HS, int VS>
 __global__ __launch_bounds__(PT) void jpeg_rgb_hv_kernel(const uint8_t* __restrict__ planes, void* __restrict__ out, long frames, int h, int w, int ph,
@@ -449,7 +399,7 @@ extern "C" int mg_jpeg_rgb_hv(const uint8_t* planes, long plane_bytes, void* out
                               const float* mean3, const float* std3, void* stream) {
     if (bad_size(frames, h, w) || bad_epilogue(epilogue) || !mean3 || !std3 || !((hs == 2 && vs == 1) || (hs == 1 && vs == 2) || (hs == 4 && vs == 1)))
         return -2;
-    // mg_jpegdec_idct_hv's planes: whole MCUs, the luma pitch a multiple of 16, the 4:4:0 chroma pitch too
+    // mg_jpegdec_idct's planes: whole MCUs, the luma pitch a multiple of 16, the 4:4:0 chroma pitch too
     const int mcux = (w + 8 * hs - 1) / (8 * hs), mcuy = (h + 8 * vs - 1) / (8 * vs);
     const int ph = mcuy * 8 * vs, yp = (mcux * 8 * hs + 15) & ~15, chh = mcuy * 8, cp = vs == 2 ? (mcux * 8 + 15) & ~15 : mcux * 8;
     if (plane_bytes != frames * ((long)ph * yp + 2L * chh * cp)) return -2;

@@ -27,26 +27,36 @@ import torch
 from .. import hip
 from ..hip import c_int, c_long
 from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, integer, resolve_device
-from .photometric import MAX_SIDE, NORM, RAW, plane_bytes
+from ._jpegfile import Unsupported, ZIGZAG, walk                  # noqa: F401  (ZIGZAG: for the callers of this module)
+from .photometric import MAX_SIDE, NORM, RAW
 
-L420, L444, GREY = 0, 1, 2                                  # MG_JPEGDEC_420 / _444 / _GREY (include/maggie_hip.h)
+L420, L444, GREY, L422, L440, L411 = 0, 1, 2, 3, 4, 5          # MG_JPEGDEC_420 / _444 / _GREY / _422 / _440 / _411 (include/maggie_hip.h)
+LUMA = {L422: (2, 1), L440: (1, 2), L411: (4, 1)}           # the luma sampling (hs, vs) of the layouts whose planes are pitched
+_HV = {L420: (2, 2), L444: (1, 1), GREY: (1, 1), **LUMA}
 THREADS, TAB_WORDS, MIN_SUB, MAX_SUB, DEFAULT_SUB = 128, 1120, 8, 4096, 8        # MG_JPEGDEC_THREADS / _TAB_WORDS / _MIN_SUB / _MAX_SUB / _DEFAULT_SUB
 MAX_BYTES = 1 << 28                                         # MG_JPEGDEC_MAX_BYTES
 STATUS = {1: 'a zig-zag index past 63', 2: 'an unassigned Huffman code', 4: 'the entropy-coded segment ends before the last block',
           8: 'the number of blocks is not MCUs x blocks per MCU', 16: 'a restart marker out of place'}
-BLOCKS_PER_MCU = {L420: 6, L444: 3, GREY: 1}
-ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
 
 
-class Unsupported(ValueError):
-    """A JPEG file outside the set the device decodes (or not a JPEG file): fall back to PIL."""
+def geometry(h, w, layout):
+    """The geometry of a frame in any of the six layouts, csrc/jpeg_common.h's: (blocks of a frame, plane bytes of a frame, luma rows, luma
+    pitch, chroma rows, chroma pitch). An MCU is 8 hs x 8 vs pixels: hs * vs luma blocks, then Cb, then Cr. The planes of 4:2:0, 4:4:4 and
+    grey are as wide as their blocks; those of the `LUMA` layouts are pitched to the widest load of a lane of mg_jpeg_rgb_hv: the luma pitch
+    is a multiple of 16 bytes and the 4:4:0 chroma pitch too."""
+    hs, vs = _HV[layout]
+    mx, my, chroma = -(-w // (8 * hs)), -(-h // (8 * vs)), 0 if layout == GREY else 2
+    yp, cp = mx * 8 * hs, mx * 8
+    if layout in LUMA:
+        yp, cp = -(-yp // 16) * 16, -(-cp // 16) * 16 if vs == 2 else cp
+    return mx * my * (hs * vs + chroma), my * 8 * (vs * yp + chroma * cp), my * 8 * vs, yp, my * 8, cp
 
 
 class JpegPlan:
-    """What `parse` found: `width`, `height`, `layout` (L420, L444 or GREY), `sampling` ((h, v) per component), `quantization` ({id: int32 (64,)
+    """What `parse` found: `width`, `height`, `layout` (one of the six), `sampling` ((h, v) per component), `quantization` ({id: int32 (64,)
     natural order}), `qtables` (int32 (3, 64): the table of each output component), `dc` / `ac` ({id: (counts uint8 (16,), values uint8 (n,))}),
     `selectors` ((dc id, ac id) per component), `restart_interval` (MCUs, 0 = none), `offset` / `length` of the entropy-coded segment."""
+    kind = 'baseline'
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -57,8 +67,8 @@ class JpegPlan:
 
     @property
     def mcus(self):
-        side = 16 if self.layout == L420 else 8
-        return ((self.width + side - 1) // side) * ((self.height + side - 1) // side)
+        hs, vs = _HV[self.layout]
+        return -(-self.width // (8 * hs)) * -(-self.height // (8 * vs))
 
 
 def _layout(sampling):
@@ -77,139 +87,62 @@ def parse(data):
     return _parse(data, _layout)
 
 
-def _parse(data, layout_of):
-    """`parse` with the accepted samplings given: `layout_of(sampling)` returns the layout or raises `Unsupported` (`jpegsamp.parse` walks the
-    same markers for its three samplings)."""
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
-    d = bytes(data)
-    n = len(d)
-    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
-        raise Unsupported('not a JPEG file (no SOI marker)')
-    quant, dc, ac = {}, {}, {}
-    frame = scan = None
-    ri = 0
-    p = 2
-    while True:
-        if p + 4 > n:
-            raise Unsupported('the file ends inside its headers')
-        if d[p] != 0xFF:
-            raise Unsupported('expected a marker at byte %d' % p)
-        m = d[p + 1]
-        if m == 0xFF:                                          # fill byte
-            p += 1
-            continue
-        if m == 0xD9:
-            raise Unsupported('EOI before any scan')
-        size = (d[p + 2] << 8) | d[p + 3]
-        seg = d[p + 4:p + 2 + size]
-        if size < 2 or p + 2 + size > n:
-            raise Unsupported('a marker segment runs past the end of the file')
-        if m == 0xC0:
-            if frame is not None:
-                raise Unsupported('more than one frame header')
-            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
-                raise Unsupported('a malformed SOF0 segment')
-            if seg[0] != 8:
-                raise Unsupported('%d-bit samples (only 8-bit baseline is decoded)' % seg[0])
-            frame = dict(height=(seg[1] << 8) | seg[2], width=(seg[3] << 8) | seg[4],
-                         comps=[(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(seg[5])])
-        elif 0xC1 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
-            names = {0xC1: 'extended sequential', 0xC2: 'progressive', 0xC3: 'lossless', 0xC9: 'arithmetic-coded sequential',
-                     0xCA: 'arithmetic-coded progressive'}
-            raise Unsupported('SOF%d (%s): only SOF0 baseline is decoded' % (m - 0xC0, names.get(m, 'differential or arithmetic')))
-        elif m == 0xCC:
-            raise Unsupported('arithmetic coding conditioning (DAC)')
-        elif m == 0xC4:
-            q = 0
-            while q < len(seg):
-                if q + 17 > len(seg):
-                    raise Unsupported('a malformed DHT segment')
-                tc, th = seg[q] >> 4, seg[q] & 15
-                counts = np.frombuffer(seg[q + 1:q + 17], np.uint8)
-                total = int(counts.sum())
-                if tc > 1 or th > 1 or total > 256 or q + 17 + total > len(seg):
-                    raise Unsupported('a malformed DHT segment (class %d, id %d)' % (tc, th))
-                code = 0
-                for l in range(16):
-                    code += int(counts[l])
-                    if code > (2 << l):
-                        raise Unsupported('a DHT table whose code lengths overflow')
-                    code <<= 1
-                (ac if tc else dc)[th] = (counts.copy(), np.frombuffer(seg[q + 17:q + 17 + total], np.uint8).copy())
-                q += 17 + total
-        elif m == 0xDB:
-            q = 0
-            while q < len(seg):
-                if seg[q] >> 4:
-                    raise Unsupported('a 16-bit quantisation table')
-                if (seg[q] & 15) > 3 or q + 65 > len(seg):
-                    raise Unsupported('a malformed DQT segment')
-                t = np.zeros(64, np.int32)
-                t[ZIGZAG] = np.frombuffer(seg[q + 1:q + 65], np.uint8)
-                quant[seg[q] & 15] = t
-                q += 65
-        elif m == 0xDD:
-            if len(seg) != 2:
-                raise Unsupported('a malformed DRI segment')
-            ri = (seg[0] << 8) | seg[1]
-        elif m == 0xDC:
-            raise Unsupported('DNL (the height is defined after the scan)')
-        elif m == 0xEE and seg[:5] == b'Adobe' and len(seg) >= 12:
-            if seg[11] != 1:
-                raise Unsupported('an Adobe APP14 marker with transform %d (only YCbCr is decoded)' % seg[11])
-        elif m == 0xDA:
-            if frame is None:
-                raise Unsupported('SOS before SOF0')
-            ns = seg[0] if seg else 0
-            if len(seg) != 4 + 2 * ns:
-                raise Unsupported('a malformed SOS segment')
-            scan = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
-            p += 2 + size
-            break
-        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
-            raise Unsupported('marker 0xFF%02X is not decoded' % m)
-        p += 2 + size
-    comps = frame['comps']
+def check_frame(frame):
+    """The frame headers both decoders take; `frame` gains `sampling`."""
+    comps, w, h = frame['comps'], frame['width'], frame['height']
     if len(comps) not in (1, 3):
         raise Unsupported('%d components (only YCbCr and greyscale are decoded)' % len(comps))
-    w, h = frame['width'], frame['height']
     if h == 0:
         raise Unsupported('DNL (the height is defined after the scan)')
     if w < 1 or w > MAX_SIDE or h > MAX_SIDE:
         raise Unsupported('%d x %d: sides of 1..%d are decoded' % (w, h, MAX_SIDE))
-    if [c[0] for c in comps] != [s[0] for s in scan]:
-        raise Unsupported('several scans, or a scan that does not hold every component in frame order')
-    sampling = tuple((c[1], c[2]) for c in comps)
-    layout = layout_of(sampling)
+    if frame['sof'] == 0xC2 and len({c[0] for c in comps}) != len(comps):
+        raise Unsupported('two components with one identifier')
+    frame['sampling'] = tuple((c[1], c[2]) for c in comps)
+
+
+def output_tables(f):
+    """int32 (3, 64): the quantisation table of each output component, or `Unsupported` where a component names one the file did not define."""
+    comps = f.frame['comps']
     for c in comps:
-        if c[3] not in quant:
+        if c[3] not in f.quant:
             raise Unsupported('quantisation table %d is not defined' % c[3])
-    for _, td, ta in scan:
-        if td > 1 or ta > 1 or td not in dc or ta not in ac:
-            raise Unsupported('a scan that selects a Huffman table that is not defined (DC %d, AC %d)' % (td, ta))
-    # the entropy-coded segment: up to the first marker that is neither a stuffed 0xFF00 nor RSTn
-    start = p
-    while True:
-        p = d.find(b'\xff', p)
-        if p < 0 or p + 1 >= n:
-            raise Unsupported('no EOI marker behind the scan')
-        if d[p + 1] == 0 or 0xD0 <= d[p + 1] <= 0xD7:
-            p += 2
-            continue
-        if d[p + 1] == 0xFF:
-            p += 1
-            continue
-        break
-    if d[p + 1] == 0xDC:
-        raise Unsupported('DNL (the height is defined after the scan)')
-    if d[p + 1] != 0xD9:
-        raise Unsupported('several scans (marker 0xFF%02X behind the first)' % d[p + 1])
-    if p - start > MAX_BYTES - MAX_SUB:
-        raise Unsupported('an entropy-coded segment of %d bytes' % (p - start))
-    qt = np.stack([quant[comps[min(k, len(comps) - 1)][3]] for k in range(3)]).astype(np.int32)
-    return JpegPlan(width=w, height=h, layout=layout, sampling=sampling, quantization=quant, qtables=qt, dc=dc, ac=ac,
-                    selectors=tuple((s[1], s[2]) for s in scan), restart_interval=ri, offset=start, length=p - start)
+    return np.stack([f.quant[comps[min(k, len(comps) - 1)][3]] for k in range(3)]).astype(np.int32)
+
+
+def rules(layout_of):
+    """(on_frame, on_scan, plan): the acceptance rules of a baseline file for `walk`, and the JpegPlan of what `walk` returns. `layout_of(sampling)`
+    returns the layout or raises `Unsupported` (`jpegsamp.parse` walks the same markers for its three samplings)."""
+    def on_frame(f):
+        pass
+
+    def on_scan(f, scan):                                      # the frame is judged here, where the single scan is known
+        check_frame(f.frame)
+        if [c[0] for c in f.frame['comps']] != [s[0] for s in scan.selectors]:
+            raise Unsupported('several scans, or a scan that does not hold every component in frame order')
+        f.frame['layout'] = layout_of(f.frame['sampling'])
+        f.qtables = output_tables(f)
+        for _, td, ta in scan.selectors:
+            if td > 1 or ta > 1 or td not in f.dc or ta not in f.ac:
+                raise Unsupported('a scan that selects a Huffman table that is not defined (DC %d, AC %d)' % (td, ta))
+
+    def plan(f):
+        scan = f.scans[0]
+        if f.next == 0xDC:
+            raise Unsupported('DNL (the height is defined after the scan)')
+        if f.next != 0xD9:
+            raise Unsupported('several scans (marker 0xFF%02X behind the first)' % f.next)
+        if scan.length > MAX_BYTES - MAX_SUB:
+            raise Unsupported('an entropy-coded segment of %d bytes' % scan.length)
+        return JpegPlan(width=f.frame['width'], height=f.frame['height'], layout=f.frame['layout'], sampling=f.frame['sampling'], quantization=f.quant,
+                        qtables=f.qtables, dc=f.dc, ac=f.ac, selectors=tuple((s[1], s[2]) for s in scan.selectors),
+                        restart_interval=f.restart_interval, offset=scan.offset, length=scan.length)
+    return on_frame, on_scan, plan
+
+
+def _parse(data, layout_of):
+    on_frame, on_scan, plan = rules(layout_of)
+    return plan(walk(data, False, on_frame, on_scan))
 
 
 _WORDS = {}                                                 # huffman_words by table: a loader's files share a handful of tables
@@ -271,31 +204,41 @@ def _sub_bytes(sub_bytes):
     return s
 
 
-def planes_size(n, h, w, layout):
-    """The bytes of the component planes between mg_jpegdec_idct and the colour kernel."""
-    if layout == L420:
-        return plane_bytes(n, h, w)
-    return n * ((h + 7) // 8 * 8) * ((w + 7) // 8 * 8) * (1 if layout == GREY else 3)
-
-
 class Decoded:
     """What `run` leaves on the device: `out`, the coefficient blocks `coef` (T, blocks, 64) int16 in scan order, the component `planes`, and
     on the host `rounds` (rounds inside workgroups, summed over the launches), `launches`, `subsequences` (the bound of the rounds) and
     `readbacks`."""
 
 
-def hv_geometry(h, w, hs, vs):
-    """The geometry of the `_hv` entries (include/maggie_hip.h): (blocks of a frame, plane bytes of a frame, luma rows, luma pitch, chroma
-    rows, chroma pitch). The luma pitch is a multiple of 16 bytes and the 4:4:0 chroma pitch too: the widest load of a lane of mg_jpeg_rgb_hv."""
-    mx, my = -(-w // (8 * hs)), -(-h // (8 * vs))
-    yp, cp = -(-mx * 8 * hs // 16) * 16, -(-mx * 8 // 16) * 16 if vs == 2 else mx * 8
-    return mx * my * (hs * vs + 2), my * 8 * (vs * yp + 2 * cp), my * 8 * vs, yp, my * 8, cp
+def finishing(r, tabs, T, h, w, layout, normalize, mean, std, out):
+    """What `run` here and `jpegprog.run` share behind the coefficients. Before any launch: `out` allocated or validated, `r.coef` (zeroed)
+    and `r.planes` allocated by `geometry`, `r.out` shaped. Returns the function that launches mg_jpegdec_idct and the colour entry of the layout."""
+    dev = tabs.device
+    nblocks, per_frame = geometry(h, w, layout)[:2]
+    coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
+    planes = torch.empty((T * per_frame,), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
+    elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('out must be a contiguous %s tensor of %d elements on %s' % ('float32' if normalize else 'uint8', T * h * w * 3, dev))
+    r.out, r.coef, r.planes = out.reshape((T, 3, h, w) if normalize else (T, h, w, 3)), coef, planes
+    size, epilogue = (c_long(T), c_int(h), c_int(w)), (c_int(NORM if normalize else RAW), float3(mean), float3(std))
+
+    def finish():
+        st = hip.stream()
+        hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), *size, c_int(layout), st)
+        if layout == L420:
+            hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), *size, *epilogue, st)
+        elif layout in LUMA:
+            hip.call('mg_jpeg_rgb_hv', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), *size, *map(c_int, LUMA[layout]), *epilogue, st)
+        else:
+            hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), *size, c_int(layout), *epilogue, st)
+    return finish
 
 
-def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, hv=None):
+def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
     """The launches themselves: `blob` uint8 device tensor holding the T segments, `recs` int32 (T, TAB_WORDS) host records whose offsets point
-    into it. `out`: a preallocated contiguous destination of the right size and dtype (else allocated). `hv`: the luma sampling (hs, vs) of
-    `jpegsamp`'s layouts, which run the `_hv` entries (`layout` is then not passed on). Returns a `Decoded`."""
+    into it. `out`: a preallocated contiguous destination of the right size and dtype (else allocated). Returns a `Decoded`."""
     S = _sub_bytes(sub_bytes)
     recs = np.ascontiguousarray(recs, np.int32).reshape(-1, TAB_WORDS)
     T = recs.shape[0]
@@ -308,7 +251,6 @@ def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGE
     nsub = max(1, -(-int(recs[:, 919].max()) // S))
     wgs = -(-nsub // THREADS)
     max_launches = wgs + 1
-    epilogue = NORM if normalize else RAW
     tabs = torch.from_numpy(recs).to(dev, non_blocking=True)
     exits = torch.empty((T, nsub), dtype=torch.int64, device=dev)
     counts = torch.empty((T, nsub), dtype=torch.int32, device=dev)
@@ -316,41 +258,20 @@ def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGE
     entries = torch.empty((T, wgs), dtype=torch.int64, device=dev)
     bounds = torch.zeros((2, T, wgs), dtype=torch.int64, device=dev)
     info = torch.zeros((4 + 2 * (max_launches + 1),), dtype=torch.int32, device=dev)
-    if hv is None:
-        nblocks = ((w + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * \
-            ((h + (15 if layout == L420 else 7)) // (16 if layout == L420 else 8)) * BLOCKS_PER_MCU[layout]
-        nplanes = planes_size(T, h, w, layout)
-        sfx, geo = '', (c_int(layout),)
-    else:
-        nblocks, per_frame = hv_geometry(h, w, *hv)[:2]
-        nplanes = T * per_frame
-        sfx, geo = '_hv', (c_int(hv[0]), c_int(hv[1]))
-    coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
-    planes = torch.empty((nplanes,), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
-    elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
-        raise ValueError('out must be a contiguous %s tensor of %d elements on %s' % ('float32' if normalize else 'uint8', T * h * w * 3, dev))
+    r = Decoded()
+    finish = finishing(r, tabs, T, h, w, layout, normalize, mean, std, out)
+    coef = r.coef
     st = hip.stream
 
     def sync(k):
-        hip.call('mg_jpegdec_sync' + sfx, hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(entries),
-                 hip.ptr(bounds), hip.ptr(info), c_int(info.numel()), c_long(T), c_int(nsub), c_int(S), *geo, c_int(k), st())
+        hip.call('mg_jpegdec_sync', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(entries),
+                 hip.ptr(bounds), hip.ptr(info), c_int(info.numel()), c_long(T), c_int(nsub), c_int(S), c_int(layout), c_int(k), st())
 
     def output():
-        hip.call('mg_jpegdec_coef' + sfx, hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(first),
-                 hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(nsub), c_int(S), c_int(h), c_int(w), *geo, st())
-        hip.call('mg_jpegdec_dcsum' + sfx, hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), c_long(T), c_int(h), c_int(w), *geo, st())
-        hip.call('mg_jpegdec_idct' + sfx, hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
-                 c_int(h), c_int(w), *geo, st())
-        if hv is not None:
-            hip.call('mg_jpeg_rgb_hv', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), *geo,
-                     c_int(epilogue), float3(mean), float3(std), st())
-        elif layout == L420:
-            hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
-        else:
-            hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),
-                     c_int(epilogue), float3(mean), float3(std), st())
+        hip.call('mg_jpegdec_coef', hip.ptr(blob), c_long(blob.numel()), hip.ptr(tabs), hip.ptr(exits), hip.ptr(counts), hip.ptr(first),
+                 hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(nsub), c_int(S), c_int(h), c_int(w), c_int(layout), st())
+        hip.call('mg_jpegdec_dcsum', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), c_long(T), c_int(h), c_int(w), c_int(layout), st())
+        finish()
 
     sync(0)
     k = 0
@@ -377,10 +298,44 @@ def run(blob, recs, h, w, layout, *, sub_bytes=None, normalize=False, mean=IMAGE
         readbacks += 1
     if host[0]:
         raise ValueError('a corrupt entropy-coded segment: ' + '; '.join(v for b, v in STATUS.items() if host[0] & b))
-    r = Decoded()
-    r.out, r.coef, r.planes = out.reshape((T, 3, h, w) if normalize else (T, h, w, 3)), coef, planes
     r.rounds, r.launches, r.subsequences, r.readbacks = int(host[3::2].sum()), k + 1, nsub, readbacks
     return r
+
+
+def datas_of(datas):
+    """`datas` checked: a non-empty sequence of the bytes of files."""
+    if isinstance(datas, (bytes, bytearray, memoryview)) or not hasattr(datas, '__len__'):
+        raise TypeError('datas must be a sequence of the bytes of JPEG files (got %s)' % type(datas).__name__)
+    if len(datas) < 1:
+        raise ValueError('datas must hold at least one file')
+    for d in datas:
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(d).__name__)
+
+
+def one_geometry(plans):
+    if any(p.geometry != plans[0].geometry for p in plans):
+        raise ValueError('the files of a clip must share one size and one sampling layout (got %s)' % sorted({p.geometry for p in plans}))
+
+
+def offsets_of(datas):
+    """The offset of each file in the buffer that holds a clip's files one behind the other."""
+    offsets = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
+    if offsets[-1] > MAX_BYTES:
+        raise Unsupported('%d bytes of files in one clip' % offsets[-1])
+    return offsets[:-1]
+
+
+def blob_of(datas, device):
+    """That buffer: a uint8 tensor on `device`."""
+    return torch.frombuffer(bytearray(b''.join(bytes(d) for d in datas)), dtype=torch.uint8).to(resolve_device(device), non_blocking=True)
+
+
+def run_files(datas, plans, device, **kw):
+    """Baseline files of one geometry and their plans -> records and blob -> `run` (`kw`: its keywords)."""
+    recs = np.stack([record(p, int(o)) for p, o in zip(plans, offsets_of(datas))])
+    h, w, layout = plans[0].geometry
+    return run(blob_of(datas, device), recs, h, w, layout, **kw)
 
 
 def _clip(datas, normalize, mean, std, device, sub_bytes):
@@ -391,16 +346,8 @@ def _clip(datas, normalize, mean, std, device, sub_bytes):
     _sub_bytes(sub_bytes)
     float3(mean), float3(std)
     plans = [parse(d) for d in datas]
-    if any(p.geometry != plans[0].geometry for p in plans):
-        raise ValueError('the files of a clip must share one size and one sampling layout (got %s)' % sorted({p.geometry for p in plans}))
-    offsets = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
-    if offsets[-1] > MAX_BYTES:
-        raise Unsupported('%d bytes of files in one clip' % offsets[-1])
-    recs = np.stack([record(p, int(o)) for p, o in zip(plans, offsets[:-1])])
-    device = resolve_device(device)
-    blob = torch.frombuffer(bytearray(b''.join(bytes(d) for d in datas)), dtype=torch.uint8).to(device, non_blocking=True)
-    h, w, layout = plans[0].geometry
-    return run(blob, recs, h, w, layout, sub_bytes=sub_bytes, normalize=normalize, mean=mean, std=std)
+    one_geometry(plans)
+    return run_files(datas, plans, device, sub_bytes=sub_bytes, normalize=normalize, mean=mean, std=std)
 
 
 def decode_clip(datas, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None, sub_bytes=None):

@@ -23,8 +23,9 @@ from .. import hip
 from ..hip import c_int, c_long
 from . import jpegdec
 from ._inputs import IMAGENET_MEAN, IMAGENET_STD, float3, resolve_device
-from .jpegdec import BLOCKS_PER_MCU, GREY, L420, L444, MAX_BYTES, Unsupported, ZIGZAG, huffman_words, planes_size
-from .photometric import MAX_SIDE, NORM, RAW
+from ._jpegfile import Scan, walk                           # noqa: F401  (Scan: for the callers of this module)
+from .jpegdec import MAX_BYTES, Unsupported, huffman_words
+from .photometric import MAX_SIDE
 
 THREADS, SCAN_WORDS, CHAIN_WORDS = 64, 480, 4               # MG_JPEGPROG_THREADS / _SCAN_WORDS / _CHAIN_WORDS (include/maggie_hip.h)
 STATUS = dict(jpegdec.STATUS)
@@ -33,21 +34,10 @@ STATUS.update({32:'a refinement symbol that is not a 1-bit value, or a value pas
 _EMPTY = (np.zeros(16, np.uint8), np.zeros(0, np.uint8))
 
 
-class Scan:
-    """One scan: `components` (indices into the frame's components, frame order), `Ss`, `Se`, `Ah`, `Al`, `dc` / `ac` (per component the table
-    (counts, values) its selector named at this SOS, None where the scan needs none), `restart_interval`, `offset` / `length` of its segment."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-    @property
-    def script(self):
-        return self.components, self.Ss, self.Se, self.Ah, self.Al
-
-
 class ProgPlan:
     """What `parse` found: `width`, `height`, `layout`, `sampling`, `quantization`, `qtables` (int32 (3, 64)) as in `jpegdec.JpegPlan`; `scans`
     (the `Scan`s in file order); `chains`: [('dc', None, [scan numbers])] + [('ac', component, [scan numbers])] per component."""
+    kind = 'progressive'
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -66,156 +56,45 @@ def parse(data):
     return _parse(data, jpegdec._layout)
 
 
+def rules(layout_of):
+    """(on_frame, on_scan, plan) of a progressive file, as `jpegdec.rules`."""
+    def on_frame(f):
+        jpegdec.check_frame(f.frame)
+        f.frame['layout'] = layout_of(f.frame['sampling'])
+
+    def on_scan(f, scan):                                      # the tables are taken by content: a later DHT may redefine an id
+        ids = [c[0] for c in f.frame['comps']]
+        if any(s[0] not in ids for s in scan.selectors):
+            raise Unsupported('a scan of a component the frame does not have')
+        comps = tuple(ids.index(s[0]) for s in scan.selectors)
+        if any(b <= a for a, b in zip(comps, comps[1:])):
+            raise Unsupported('a scan whose components are not in frame order')
+        need_dc, need_ac = scan.Ss == 0 and scan.Ah == 0, scan.Ss > 0
+        for _, td, ta in scan.selectors:
+            if (need_dc and td not in f.dc) or (need_ac and ta not in f.ac):
+                raise Unsupported('a scan that selects a Huffman table that is not defined (DC %d, AC %d)' % (td, ta))
+        scan.components, scan.first = comps, scan.Ah == 0
+        scan.dc = [f.dc[td] if need_dc else None for _, td, _ in scan.selectors]
+        scan.ac = [f.ac[ta] if need_ac else None for _, _, ta in scan.selectors]
+
+    def plan(f):
+        if f.frame is None or not f.scans:
+            raise Unsupported('EOI before any scan')
+        ncomp = len(f.frame['comps'])
+        qt = jpegdec.output_tables(f)
+        _check_progression(f.scans, ncomp)
+        if f.nbytes > MAX_BYTES:
+            raise Unsupported('a file of %d bytes' % f.nbytes)
+        chains = [('dc', None, [k for k, s in enumerate(f.scans) if s.Ss == 0])]
+        chains += [('ac', c, [k for k, s in enumerate(f.scans) if s.Ss > 0 and s.components == (c,)]) for c in range(ncomp)]
+        return ProgPlan(width=f.frame['width'], height=f.frame['height'], layout=f.frame['layout'], sampling=f.frame['sampling'], quantization=f.quant,
+                        qtables=qt, scans=f.scans, chains=chains)
+    return on_frame, on_scan, plan
+
+
 def _parse(data, layout_of):
-    """`parse` with the accepted samplings given, as `jpegdec._parse`."""
-    if not isinstance(data, (bytes, bytearray, memoryview)):
-        raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(data).__name__)
-    d = bytes(data)
-    n = len(d)
-    if n < 4 or d[0] != 0xFF or d[1] != 0xD8:
-        raise Unsupported('not a JPEG file (no SOI marker)')
-    quant, dc, ac = {}, {}, {}
-    frame, scans, ri, p = None, [], 0, 2
-    while True:
-        if p + 2 > n:
-            raise Unsupported('the file ends without an EOI marker')
-        if d[p] != 0xFF:
-            raise Unsupported('expected a marker at byte %d' % p)
-        m = d[p + 1]
-        if m == 0xFF:                                          # fill byte
-            p += 1
-            continue
-        if m == 0xD9:
-            break
-        if p + 4 > n:
-            raise Unsupported('the file ends inside its headers')
-        size = (d[p + 2] << 8) | d[p + 3]
-        seg = d[p + 4:p + 2 + size]
-        if size < 2 or p + 2 + size > n:
-            raise Unsupported('a marker segment runs past the end of the file')
-        if m == 0xC2:
-            if frame is not None:
-                raise Unsupported('more than one frame header')
-            if len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
-                raise Unsupported('a malformed SOF2 segment')
-            if seg[0] != 8:
-                raise Unsupported('%d-bit samples (only 8-bit progressive is decoded)' % seg[0])
-            frame = dict(height=(seg[1] << 8) | seg[2], width=(seg[3] << 8) | seg[4],
-                         comps=[(seg[6 + 3 * k], seg[7 + 3 * k] >> 4, seg[7 + 3 * k] & 15, seg[8 + 3 * k]) for k in range(seg[5])])
-            _check_frame(frame, layout_of)
-        elif m in (0xC0, 0xC1):
-            raise Unsupported('SOF%d (sequential): use jpegdec for baseline files' % (m - 0xC0))
-        elif 0xC3 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
-            names = {0xC3: 'lossless', 0xC9: 'arithmetic-coded sequential', 0xCA: 'arithmetic-coded progressive'}
-            raise Unsupported('SOF%d (%s): only SOF2 with Huffman coding is decoded' % (m - 0xC0, names.get(m, 'differential or arithmetic')))
-        elif m == 0xCC:
-            raise Unsupported('arithmetic coding conditioning (DAC)')
-        elif m == 0xC4:
-            q = 0
-            while q < len(seg):
-                if q + 17 > len(seg):
-                    raise Unsupported('a malformed DHT segment')
-                tc, th = seg[q] >> 4, seg[q] & 15
-                counts = np.frombuffer(seg[q + 1:q + 17], np.uint8)
-                total = int(counts.sum())
-                if tc > 1 or th > 3 or total > 256 or q + 17 + total > len(seg):
-                    raise Unsupported('a malformed DHT segment (class %d, id %d)' % (tc, th))
-                code = 0
-                for l in range(16):
-                    code += int(counts[l])
-                    if code > (2 << l):
-                        raise Unsupported('a DHT table whose code lengths overflow')
-                    code <<= 1
-                (ac if tc else dc)[th] = (counts.copy(), np.frombuffer(seg[q + 17:q + 17 + total], np.uint8).copy())
-                q += 17 + total
-        elif m == 0xDB:
-            if scans:
-                raise Unsupported('a DQT segment behind the first scan')
-            q = 0
-            while q < len(seg):
-                if seg[q] >> 4:
-                    raise Unsupported('a 16-bit quantisation table')
-                if (seg[q] & 15) > 3 or q + 65 > len(seg):
-                    raise Unsupported('a malformed DQT segment')
-                t = np.zeros(64, np.int32)
-                t[ZIGZAG] = np.frombuffer(seg[q + 1:q + 65], np.uint8)
-                quant[seg[q] & 15] = t
-                q += 65
-        elif m == 0xDD:
-            if len(seg) != 2:
-                raise Unsupported('a malformed DRI segment')
-            ri = (seg[0] << 8) | seg[1]
-        elif m == 0xDC:
-            raise Unsupported('DNL (the height is defined after the scan)')
-        elif m == 0xEE and seg[:5] == b'Adobe' and len(seg) >= 12:
-            if seg[11] != 1:
-                raise Unsupported('an Adobe APP14 marker with transform %d (only YCbCr is decoded)' % seg[11])
-        elif m == 0xDA:
-            if frame is None:
-                raise Unsupported('SOS before SOF2')
-            ns = seg[0] if seg else 0
-            if ns < 1 or len(seg) != 4 + 2 * ns:
-                raise Unsupported('a malformed SOS segment')
-            ids = [c[0] for c in frame['comps']]
-            sel = [(seg[1 + 2 * k], seg[2 + 2 * k] >> 4, seg[2 + 2 * k] & 15) for k in range(ns)]
-            if any(s[0] not in ids for s in sel):
-                raise Unsupported('a scan of a component the frame does not have')
-            comps = tuple(ids.index(s[0]) for s in sel)
-            if any(b <= a for a, b in zip(comps, comps[1:])):
-                raise Unsupported('a scan whose components are not in frame order')
-            Ss, Se, Ah, Al = seg[1 + 2 * ns], seg[2 + 2 * ns], seg[3 + 2 * ns] >> 4, seg[3 + 2 * ns] & 15
-            first, need_dc, need_ac = Ah == 0, Ss == 0 and Ah == 0, Ss > 0
-            for _, td, ta in sel:
-                if (need_dc and td not in dc) or (need_ac and ta not in ac):
-                    raise Unsupported('a scan that selects a Huffman table that is not defined (DC %d, AC %d)' % (td, ta))
-            start = p + 2 + size
-            p = start
-            while True:                                        # up to the first marker that is neither a stuffed 0xFF00 nor RSTn
-                p = d.find(b'\xff', p)
-                if p < 0 or p + 1 >= n:
-                    raise Unsupported('no EOI marker behind the scan')
-                if d[p + 1] == 0 or 0xD0 <= d[p + 1] <= 0xD7:
-                    p += 2
-                    continue
-                if d[p + 1] == 0xFF:
-                    p += 1
-                    continue
-                break
-            scans.append(Scan(components=comps, Ss=Ss, Se=Se, Ah=Ah, Al=Al, dc=[dc[td] if need_dc else None for _, td, _ in sel],
-                              ac=[ac[ta] if need_ac else None for _, _, ta in sel], restart_interval=ri, offset=start, length=p - start,
-                              first=first))
-            continue
-        elif not (0xE0 <= m <= 0xEF or m == 0xFE):
-            raise Unsupported('marker 0xFF%02X is not decoded' % m)
-        p += 2 + size
-    if frame is None or not scans:
-        raise Unsupported('EOI before any scan')
-    comps = frame['comps']
-    for c in comps:
-        if c[3] not in quant:
-            raise Unsupported('quantisation table %d is not defined' % c[3])
-    _check_progression(scans, len(comps))
-    if n > MAX_BYTES:
-        raise Unsupported('a file of %d bytes' % n)
-    chains = [('dc', None, [k for k, s in enumerate(scans) if s.Ss == 0])]
-    chains += [('ac', c, [k for k, s in enumerate(scans) if s.Ss > 0 and s.components == (c,)]) for c in range(len(comps))]
-    qt = np.stack([quant[comps[min(k, len(comps) - 1)][3]] for k in range(3)]).astype(np.int32)
-    return ProgPlan(width=frame['width'], height=frame['height'], layout=frame['layout'], sampling=frame['sampling'], quantization=quant, qtables=qt,
-                    scans=scans, chains=chains)
-
-
-def _check_frame(frame, layout_of):
-    comps, w, h = frame['comps'], frame['width'], frame['height']
-    if len(comps) not in (1, 3):
-        raise Unsupported('%d components (only YCbCr and greyscale are decoded)' % len(comps))
-    if h == 0:
-        raise Unsupported('DNL (the height is defined after the scan)')
-    if w < 1 or w > MAX_SIDE or h > MAX_SIDE:
-        raise Unsupported('%d x %d: sides of 1..%d are decoded' % (w, h, MAX_SIDE))
-    if len({c[0] for c in comps}) != len(comps):
-        raise Unsupported('two components with one identifier')
-    sampling = tuple((c[1], c[2]) for c in comps)
-    frame.update(sampling=sampling, layout=layout_of(sampling))
+    on_frame, on_scan, plan = rules(layout_of)
+    return plan(walk(data, True, on_frame, on_scan))
 
 
 def _check_progression(scans, ncomp):
@@ -284,11 +163,10 @@ class Decoded:
     (waves of the chain launch), `launches` (kernel launches of the call) and `readbacks`."""
 
 
-def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None, hv=None):
+def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None):
     """The launches themselves: `blob` uint8 device tensor holding the T files, `scans` int32 (S, SCAN_WORDS) and `chains` int32 (C, CHAIN_WORDS)
     host records whose offsets point into it (`records`), `qtables` int32 (T, 3, 64). `out`: a preallocated contiguous destination of the right
-    size and dtype (else allocated). `hv`: the luma sampling (hs, vs) of `jpegsamp`'s layouts, which run the `_hv` entries (`layout` is then not
-    passed on). Returns a `Decoded`."""
+    size and dtype (else allocated). Returns a `Decoded`."""
     scans = np.ascontiguousarray(scans, np.int32).reshape(-1, SCAN_WORDS)
     chains = np.ascontiguousarray(chains, np.int32).reshape(-1, CHAIN_WORDS)
     qtables = np.ascontiguousarray(qtables, np.int32).reshape(-1, 192)
@@ -297,8 +175,8 @@ def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMA
     hip.need_cuda(blob)
     if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
         raise TypeError('blob must be a contiguous 1-D uint8 tensor')
-    if (hv is None and layout not in BLOCKS_PER_MCU) or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
-        raise ValueError('h, w must be in 1..%d and layout one of L420, L444, GREY' % MAX_SIDE)
+    if layout not in jpegdec._HV or not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+        raise ValueError('h, w must be in 1..%d and layout one of the six of jpegdec' % MAX_SIDE)
     if T < 1 or len(scans) < 1 or len(chains) < 1 or blob.numel() > MAX_BYTES:
         raise ValueError('at least one file, one scan and one chain, and at most %d bytes' % MAX_BYTES)
     if (scans[:, 456] < 0).any() or (scans[:, 457] < 0).any() or int((scans[:, 456].astype(np.int64) + scans[:, 457]).max()) > blob.numel():
@@ -306,80 +184,33 @@ def run(blob, scans, chains, qtables, h, w, layout, *, normalize=False, mean=IMA
     if (chains[:, 0] < 0).any() or (chains[:, 0] >= T).any() or (chains[:, 1:3] < 0).any() or \
             int((chains[:, 1].astype(np.int64) + chains[:, 2]).max()) > len(scans):
         raise ValueError('a chain lies outside the scan records or the frames')
-    epilogue = NORM if normalize else RAW
     tabs_host = np.zeros((T, jpegdec.TAB_WORDS), np.int32)
     tabs_host[:, 928:1120] = qtables
     tabs = torch.from_numpy(tabs_host).to(dev, non_blocking=True)
     d_scans = torch.from_numpy(scans).to(dev, non_blocking=True)
     d_chains = torch.from_numpy(chains).to(dev, non_blocking=True)
     info = torch.zeros((T,), dtype=torch.int32, device=dev)
-    if hv is None:
-        side = 16 if layout == L420 else 8
-        nblocks = ((w + side - 1) // side) * ((h + side - 1) // side) * BLOCKS_PER_MCU[layout]
-        nplanes = planes_size(T, h, w, layout)
-    else:
-        nblocks, per_frame = jpegdec.hv_geometry(h, w, *hv)[:2]
-        nplanes = T * per_frame
-    coef = torch.zeros((T, nblocks, 64), dtype=torch.int16, device=dev)
-    planes = torch.empty((nplanes,), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=dev)
-    elif out.numel() != T * h * w * 3 or out.dtype != (torch.float32 if normalize else torch.uint8) or not out.is_contiguous() or out.device != dev:
-        raise ValueError('out must be a contiguous %s tensor of %d elements on %s' % ('float32' if normalize else 'uint8', T * h * w * 3, dev))
-    st = hip.stream
-    launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout, hv)
-    if hv is not None:
-        hip.call('mg_jpegdec_idct_hv', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
-                 c_int(h), c_int(w), c_int(hv[0]), c_int(hv[1]), st())
-        hip.call('mg_jpeg_rgb_hv', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(hv[0]), c_int(hv[1]),
-                 c_int(epilogue), float3(mean), float3(std), st())
-    else:
-        hip.call('mg_jpegdec_idct', hip.ptr(coef), c_long(coef.numel()), hip.ptr(tabs), hip.ptr(planes), c_long(planes.numel()), c_long(T),
-                 c_int(h), c_int(w), c_int(layout), st())
-        if layout == L420:
-            hip.call('mg_jpeg_rgb', hip.ptr(planes), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(epilogue), float3(mean), float3(std), st())
-        else:
-            hip.call('mg_jpegdec_rgb', hip.ptr(planes), c_long(planes.numel()), hip.ptr(out), c_long(T), c_int(h), c_int(w), c_int(layout),
-                     c_int(epilogue), float3(mean), float3(std), st())
+    r = Decoded()
+    finish = jpegdec.finishing(r, tabs, T, h, w, layout, normalize, mean, std, out)
+    launch_chains(blob, d_scans, d_chains, r.coef, info, T, h, w, layout)
+    finish()
     host = info.cpu().numpy()
     for t in np.flatnonzero(host):
         raise ValueError('a corrupt entropy-coded segment (file %d): %s' % (t, '; '.join(v for b, v in STATUS.items() if host[t] & b)))
-    r = Decoded()
-    r.out, r.coef, r.planes = out.reshape((T, 3, h, w) if normalize else (T, h, w, 3)), coef, planes
     r.chains, r.launches, r.readbacks = len(chains), 3, 1
     return r
 
 
-def launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout, hv=None):
+def launch_chains(blob, d_scans, d_chains, coef, info, T, h, w, layout):
     """The chain launch alone (tools/jpegprog_bench.py times subsets of the chains with it): device tensors throughout."""
-    geo = (c_int(layout),) if hv is None else (c_int(hv[0]), c_int(hv[1]))
-    hip.call('mg_jpegprog_chains' if hv is None else 'mg_jpegprog_chains_hv', hip.ptr(blob), c_long(blob.numel()), hip.ptr(d_scans),
-             c_long(d_scans.shape[0]), hip.ptr(d_chains), c_long(d_chains.shape[0]), hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T),
-             c_int(h), c_int(w), *geo, hip.stream())
-
-
-def _datas(datas):
-    if isinstance(datas, (bytes, bytearray, memoryview)) or not hasattr(datas, '__len__'):
-        raise TypeError('datas must be a sequence of the bytes of JPEG files (got %s)' % type(datas).__name__)
-    if len(datas) < 1:
-        raise ValueError('datas must hold at least one file')
-    for d in datas:
-        if not isinstance(d, (bytes, bytearray, memoryview)):
-            raise TypeError('data must be the bytes of a JPEG file (got %s)' % type(d).__name__)
-
-
-def _one_geometry(plans):
-    if any(p.geometry != plans[0].geometry for p in plans):
-        raise ValueError('the files of a clip must share one size and one sampling layout (got %s)' % sorted({p.geometry for p in plans}))
+    hip.call('mg_jpegprog_chains', hip.ptr(blob), c_long(blob.numel()), hip.ptr(d_scans), c_long(d_scans.shape[0]), hip.ptr(d_chains),
+             c_long(d_chains.shape[0]), hip.ptr(coef), c_long(coef.numel()), hip.ptr(info), c_long(T), c_int(h), c_int(w), c_int(layout), hip.stream())
 
 
 def pack(plans, datas):
     """The host side of a clip: (file bytes joined, scan records, chain records with the longest chains first, quantisation tables)."""
-    offsets = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
-    if offsets[-1] > MAX_BYTES:
-        raise Unsupported('%d bytes of files in one clip' % offsets[-1])
     scans, chains, first = [], [], 0
-    for t, (p, o) in enumerate(zip(plans, offsets[:-1])):
+    for t, (p, o) in enumerate(zip(plans, jpegdec.offsets_of(datas))):
         s, c = records(p, int(o), t, first)
         scans.append(s)
         chains.append(c)
@@ -390,16 +221,19 @@ def pack(plans, datas):
     return b''.join(bytes(d) for d in datas), scans, chains, np.stack([p.qtables for p in plans])
 
 
+def run_files(datas, plans, device, **kw):
+    """Progressive files of one geometry and their plans -> records and blob -> `run` (`kw`: its keywords)."""
+    joined, scans, chains, qt = pack(plans, datas)
+    h, w, layout = plans[0].geometry
+    return run(jpegdec.blob_of([joined], device), scans, chains, qt, h, w, layout, **kw)
+
+
 def _clip(datas, normalize, mean, std, device, out=None, plans=None):
-    _datas(datas)
+    jpegdec.datas_of(datas)
     float3(mean), float3(std)
     plans = [parse(d) for d in datas] if plans is None else plans
-    _one_geometry(plans)
-    joined, scans, chains, qt = pack(plans, datas)
-    device = resolve_device(device)
-    blob = torch.frombuffer(bytearray(joined), dtype=torch.uint8).to(device, non_blocking=True)
-    h, w, layout = plans[0].geometry
-    return run(blob, scans, chains, qt, h, w, layout, normalize=normalize, mean=mean, std=std, out=out)
+    jpegdec.one_geometry(plans)
+    return run_files(datas, plans, device, normalize=normalize, mean=mean, std=std, out=out)
 
 
 def decode_clip(datas, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
@@ -425,48 +259,57 @@ def decode_stats(datas, *, device=None):
 
 def _baseline(datas, plans, normalize, mean, std, device, out):
     """`jpegdec`'s clip into `out` (jpegdec.run's own `out=`)."""
-    offsets = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
-    if offsets[-1] > MAX_BYTES:
-        raise Unsupported('%d bytes of files in one clip' % offsets[-1])
-    recs = np.stack([jpegdec.record(p, int(o)) for p, o in zip(plans, offsets[:-1])])
-    blob = torch.frombuffer(bytearray(b''.join(bytes(d) for d in datas)), dtype=torch.uint8).to(device, non_blocking=True)
-    h, w, layout = plans[0].geometry
-    return jpegdec.run(blob, recs, h, w, layout, normalize=normalize, mean=mean, std=std, out=out)
+    return jpegdec.run_files(datas, plans, device, normalize=normalize, mean=mean, std=std, out=out)
+
+
+def load_routes(datas, routes, one_layout, normalize, mean, std, device):
+    """`load_clip` here and in `jpegsamp`. `routes`: [(parse, run)] -- a file goes to the first whose `parse` accepts it (if none does, the
+    `Unsupported` of the first propagates), and `run(files, plans, normalize, mean, std, device, out)` decodes a group of files of one route,
+    kind and layout into its slice of the result. `one_layout`: the files share size AND layout and the groups run in the order of the routes;
+    else they share the size and the groups run in the order in which their first files come. `device`: a function, called once parsing is done."""
+    jpegdec.datas_of(datas)
+    float3(mean), float3(std)
+
+    def first_route(d):
+        for which, (accepts, _) in enumerate(routes):
+            try:
+                return which, accepts(d)
+            except Unsupported as e:
+                refusal = e if which == 0 else refusal
+        raise refusal from None
+    found = [first_route(d) for d in datas]
+    sizes = sorted({p.geometry[:2] for _, p in found})
+    if one_layout:
+        jpegdec.one_geometry([p for _, p in found])
+    elif len(sizes) > 1:
+        raise ValueError('the files of a clip must share one size (got %s)' % sizes)
+    device = device()
+    (h, w), T = sizes[0], len(datas)
+    groups = {}
+    for k, (which, p) in enumerate(found):
+        groups.setdefault((which, p.kind, p.layout), []).append(k)
+    keys = sorted(groups, key=(lambda g: g[0]) if one_layout else (lambda g: groups[g][0]))
+    order = [k for key in keys for k in groups[key]]
+    out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=device)
+    at = 0
+    for key in keys:
+        ks = groups[key]
+        routes[key[0]][1]([datas[k] for k in ks], [found[k][1] for k in ks], normalize, mean, std, device, out[at:at + len(ks)])
+        at += len(ks)
+    if order == list(range(T)):
+        return out
+    back = np.empty(T, np.int64)
+    back[order] = np.arange(T)
+    return out[torch.from_numpy(back).to(device)]
 
 
 def load_clip(datas, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):
     """`decode_clip` for whatever a loader finds: each file goes the way of the parser that accepts it (`jpegdec.parse` first, then `parse`; if
     neither does, the `Unsupported` of `jpegdec.parse` propagates). The baseline files are decoded in one set of launches and the progressive
     files in another, into slices of one tensor; the result is in the order of `datas`."""
-    _datas(datas)
-    float3(mean), float3(std)
-    kinds, plans = [], []
-    for d in datas:
-        try:
-            plans.append(jpegdec.parse(d))
-            kinds.append(0)
-        except Unsupported as e:
-            try:
-                plans.append(parse(d))
-            except Unsupported:
-                raise e from None
-            kinds.append(1)
-    _one_geometry(plans)
-    device = resolve_device(device)
-    h, w, _ = plans[0].geometry
-    T = len(datas)
-    order = [k for k in range(T) if kinds[k] == 0] + [k for k in range(T) if kinds[k] == 1]
-    nb = kinds.count(0)
-    out = torch.empty((T, 3, h, w) if normalize else (T, h, w, 3), dtype=torch.float32 if normalize else torch.uint8, device=device)
-    if nb:
-        _baseline([datas[k] for k in order[:nb]], [plans[k] for k in order[:nb]], normalize, mean, std, device, out[:nb])
-    if nb < T:
-        _clip([datas[k] for k in order[nb:]], normalize, mean, std, device, out=out[nb:], plans=[plans[k] for k in order[nb:]])
-    if order == list(range(T)):
-        return out
-    back = np.empty(T, np.int64)
-    back[order] = np.arange(T)
-    return out[torch.from_numpy(back).to(device)]
+    routes = [(jpegdec.parse, lambda *a: _baseline(*a)),
+              (parse, lambda files, plans, n, m, s, dev, out: _clip(files, n, m, s, dev, out=out, plans=plans))]
+    return load_routes(datas, routes, True, normalize, mean, std, lambda: resolve_device(device))
 
 
 def load(data, *, normalize=False, mean=IMAGENET_MEAN, std=IMAGENET_STD, device=None):

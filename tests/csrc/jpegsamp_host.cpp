@@ -1,11 +1,11 @@
 // The decode path of maggie_amd/utils/jpegsamp.py compiled for the host: maggie_amd/csrc/jpegdec.hip, jpegprog.hip and photometric.hip, the
 // kernel sources themselves, one thread per GPU thread, a barrier for __syncthreads, the ballot through a shared array, the workgroups of a
 // launch one after the other. Built with -fsanitize=address,undefined -pthread by tests/test_jpegsamp_cpu.py and run on buffers of exactly the
-// sizes the `_hv` entry points are told, so that an access outside them, or a wide load or store off its alignment, stops the program.
+// sizes the entry points are told, so that an access outside them, or a wide load or store off its alignment, stops the program.
 // Not a GPU program: nothing here is launched.
 //
-//   jpegsamp_host IN OUT   IN: int32 ncases, then per case int32 {kind (0 baseline, 1 progressive), h, w, hs, vs, sub_bytes, frames, nscans,
-//                          nchains, blob_bytes}, int32 recs[frames][1120] (jpegdec's records; a progressive case reads the quantisation tables
+//   jpegsamp_host IN OUT   IN: int32 ncases, then per case int32 {kind (0 baseline, 1 progressive), h, w, layout (MG_JPEGDEC_422 / _440 / _411), 0,
+//                          sub_bytes, frames, nscans, nchains, blob_bytes}, int32 recs[frames][1120] (jpegdec's records; a progressive case reads the quantisation tables
 //                          from them), progressive: int32 scans[nscans][480], int32 chains[nchains][4]; then the blob.
 //                          OUT: per case int32 {rc, status, n_coef, n_planes, n_rgb}, int16 coef, uint8 planes, uint8 rgb (raw epilogue),
 //                          float norm[n_rgb] (the ToTensor + Normalize epilogue): the host loops of jpegdec.py / jpegprog.py `run`.
@@ -149,7 +149,9 @@ int main(int argc, char** argv) {
     for (int c = 0; c < ncases && rc_main == 0; ++c) {
         int32_t hd[10];
         if (!rd(in, hd, sizeof hd)) { rc_main = 2; break; }
-        const int kind = hd[0], h = hd[1], w = hd[2], hs = hd[3], vs = hd[4], S = hd[5];
+        const int kind = hd[0], h = hd[1], w = hd[2], layout = hd[3], S = hd[5];
+        if (layout < MG_JPEGDEC_422 || layout > MG_JPEGDEC_411) { rc_main = 2; break; }
+        const int hs = layout == MG_JPEGDEC_422 ? 2 : (layout == MG_JPEGDEC_411 ? 4 : 1), vs = layout == MG_JPEGDEC_440 ? 2 : 1;
         const long T = hd[6], nscans = hd[7], nchains = hd[8], nbytes = hd[9];
         Exact<int32_t> recs((size_t)T * MG_JPEGDEC_TAB_WORDS), scans((size_t)nscans * MG_JPEGPROG_SCAN_WORDS);
         Exact<int32_t> chains((size_t)nchains * MG_JPEGPROG_CHAIN_WORDS);
@@ -167,7 +169,7 @@ int main(int argc, char** argv) {
         const float mean[3] = {0.485f, 0.456f, 0.406f}, std3[3] = {0.229f, 0.224f, 0.225f};
         int rc = 0, status = 0;
         auto finish = [&]() {
-            int r = mg_jpegdec_idct_hv(coef.p, (long)coef.n, recs.p, planes.p, pb, T, h, w, hs, vs, nullptr);
+            int r = mg_jpegdec_idct(coef.p, (long)coef.n, recs.p, planes.p, pb, T, h, w, layout, nullptr);
             if (!r) r = mg_jpeg_rgb_hv(planes.p, pb, rgb.p, T, h, w, hs, vs, MG_PHOTO_RAW, mean, std3, nullptr);
             if (!r) r = mg_jpeg_rgb_hv(planes.p, pb, norm.p, T, h, w, hs, vs, MG_PHOTO_NORM, mean, std3, nullptr);
             return r;
@@ -181,13 +183,13 @@ int main(int argc, char** argv) {
             Exact<int32_t> counts((size_t)T * nsub), first((size_t)T * nsub), info((size_t)info_words, true);
             int k = 0;
             auto sync = [&](int launch) {
-                return mg_jpegdec_sync_hv(blob.p, nbytes, recs.p, exits.p, counts.p, entries.p, bounds.p, info.p, info_words, T, nsub, S, hs, vs, launch,
-                                          nullptr);
+                return mg_jpegdec_sync(blob.p, nbytes, recs.p, exits.p, counts.p, entries.p, bounds.p, info.p, info_words, T, nsub, S, layout, launch,
+                                       nullptr);
             };
             auto output = [&]() {
-                int r = mg_jpegdec_coef_hv(blob.p, nbytes, recs.p, exits.p, counts.p, first.p, coef.p, (long)coef.n, info.p, T, nsub, S, h, w, hs, vs,
-                                           nullptr);
-                if (!r) r = mg_jpegdec_dcsum_hv(coef.p, (long)coef.n, recs.p, T, h, w, hs, vs, nullptr);
+                int r = mg_jpegdec_coef(blob.p, nbytes, recs.p, exits.p, counts.p, first.p, coef.p, (long)coef.n, info.p, T, nsub, S, h, w, layout,
+                                        nullptr);
+                if (!r) r = mg_jpegdec_dcsum(coef.p, (long)coef.n, recs.p, T, h, w, layout, nullptr);
                 return r ? r : finish();
             };
             rc = sync(0);
@@ -208,7 +210,7 @@ int main(int argc, char** argv) {
             status = info.p[0];
         } else {
             Exact<int32_t> info((size_t)T, true);
-            rc = mg_jpegprog_chains_hv(blob.p, nbytes, scans.p, nscans, chains.p, nchains, coef.p, (long)coef.n, info.p, T, h, w, hs, vs, nullptr);
+            rc = mg_jpegprog_chains(blob.p, nbytes, scans.p, nscans, chains.p, nchains, coef.p, (long)coef.n, info.p, T, h, w, layout, nullptr);
             if (!rc) rc = finish();
             for (long t = 0; t < T; ++t) status |= info.p[t];
         }

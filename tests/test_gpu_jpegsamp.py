@@ -1,5 +1,5 @@
-"""The device decoder of the other chroma samplings (maggie_amd.utils.jpegsamp: 4:2:2, 4:4:0, 4:1:1; the `_hv` entries of csrc/jpegdec.hip,
-jpegprog.hip and photometric.hip) against the restatement of tests/jpegsamp_restatement.py, which tests/test_jpegsamp_cpu.py holds against
+"""The device decoder of the other chroma samplings (maggie_amd.utils.jpegsamp: 4:2:2, 4:4:0, 4:1:1; layouts 3 to 5 of csrc/jpegdec.hip and
+jpegprog.hip, and mg_jpeg_rgb_hv of photometric.hip) against the restatement of tests/jpegsamp_restatement.py, which tests/test_jpegsamp_cpu.py holds against
 Pillow itself: the coefficients first, then the component planes, then the pixels, so that a wrong pixel points at the right kernel.
 Well-formed streams only; every comparison is exact."""
 import os
@@ -119,17 +119,16 @@ def test_odd_offset_inside_a_larger_buffer_and_guarded_outputs(name):
     data, coef, _, px = ref(name)
     plan = jpegsamp.parse(data)
     h, w, layout = plan.geometry
-    hv = jpegsamp.LUMA[layout]
     for pad in (1, 3, 7):
         blob = torch.from_numpy(np.frombuffer(b'\xff' * pad + data + b'\xff\x00\xd0' * 11, np.uint8).copy()).cuda()
         for normalize in (False, True):
             n = h * w * 3
             guard = torch.full((n + 64,), 7, dtype=torch.float32 if normalize else torch.uint8, device='cuda')
             if plan.kind == 'baseline':
-                r = jpegdec.run(blob, jpegdec.record(plan, pad)[None], h, w, layout, sub_bytes=29, normalize=normalize, out=guard[13:13 + n], hv=hv)
+                r = jpegdec.run(blob, jpegdec.record(plan, pad)[None], h, w, layout, sub_bytes=29, normalize=normalize, out=guard[13:13 + n])
             else:
                 scans, chains = jpegprog.records(plan, pad, 0, 0)
-                r = jpegprog.run(blob, scans, chains, plan.qtables[None], h, w, layout, normalize=normalize, out=guard[13:13 + n], hv=hv)
+                r = jpegprog.run(blob, scans, chains, plan.qtables[None], h, w, layout, normalize=normalize, out=guard[13:13 + n])
             assert np.array_equal(r.coef.cpu().numpy()[0], coef)
             got = guard.cpu().numpy()
             assert (got[:13] == 7).all() and (got[13 + n:] == 7).all()
@@ -156,10 +155,11 @@ def test_load_clip_of_a_mixed_list_equals_pillow_frame_by_frame(monkeypatch):
     calls = []
     for mod, fn in ((jpegdec, 'run'), (jpegprog, 'run')):
         real = getattr(mod, fn)
-        monkeypatch.setattr(mod, fn, lambda *a, _real=real, _m=mod.__name__.rsplit('.', 1)[1], **k: (calls.append((_m, k.get('hv'))), _real(*a, **k))[1])
+        at = 4 if mod is jpegdec else 6                                      # where `layout` stands among run's arguments
+        monkeypatch.setattr(mod, fn, lambda *a, _real=real, _m=mod.__name__.rsplit('.', 1)[1], _at=at, **k: (calls.append((_m, a[_at])), _real(*a, **k))[1])
     out = jpegsamp.load_clip(datas)
     assert out.shape == want.shape and out.dtype == torch.uint8 and np.array_equal(out.cpu().numpy(), want)
-    assert sorted(calls, key=str) == sorted([('jpegprog', (2, 1)), ('jpegdec', None), ('jpegdec', (2, 1))], key=str)      # one launch set per group
+    assert calls == [('jpegprog', jpegsamp.L422), ('jpegdec', jpegdec.L420), ('jpegdec', jpegsamp.L422)]      # one launch set per group
     norm = jpegsamp.load_clip(datas, normalize=True)
     assert np.array_equal(norm.cpu().numpy(), R.P.normalize(want, IMAGENET_MEAN, IMAGENET_STD))
     for d, y in zip(datas, want):
@@ -172,3 +172,35 @@ def test_decode_feeds_resize_short_pad():
         a = geometry.resize_short_pad(jpegsamp.decode_clip([data]), short_size=96, divisor=32)
         b = geometry.resize_short_pad(R.pillow(data)[None], short_size=96, divisor=32)
         assert a[0].shape == b[0].shape and torch.equal(a[0], b[0])
+
+
+def test_load_clip_crosses_all_six_layouts_in_both_kinds(monkeypatch):
+    """One baseline and one progressive 37 x 53 file of each of the six layouts, from the case lists of the three restatements (each has all
+    its kinds at 37 x 53, the progressive grey file included), shuffled with a fixed seed: every frame equals its restatement's pixels, and
+    `jpegdec.run` and `jpegprog.run` are each entered once per layout. Twelve groups of one file each come out in input order whatever the
+    shuffle, so the same clip is then decoded with every file twice, the second copies shuffled among the first: still twelve launch sets,
+    and the frames have to be permuted back."""
+    import jpegprog_restatement as J
+    files = []
+    for mode in (2, 0, 'L'):
+        files.append((R, R.stream(*R.CASES['37x53_uniform_%s_qua90' % mode])))
+        files.append((J, J.stream(*J.CASES['37x53_uniform_%s_q90' % mode])))
+    for name in ('422_37x53_uniform_base_qua90_ri3', '440_37x53_uniform_base_qua90_ri3', '411_37x53_uniform_base_qua90_ri3',
+                 '422_37x53_uniform_pillow_proT_qua90_rsb1', '440_37x53_binary_prog_qua1', '411_37x53_binary_prog_qua1'):
+        files.append((S, S.stream(name)))
+    want = [m.pixels(d, m.coefficients(d)) for m, d in files]
+    assert len(files) == 12 and all(px.shape == (37, 53, 3) for px in want)
+    calls = []
+    for mod, at in ((jpegdec, 4), (jpegprog, 6)):                          # where `layout` stands among run's arguments
+        real = mod.run
+        monkeypatch.setattr(mod, 'run', lambda *a, _real=real, _m=mod.__name__.rsplit('.', 1)[1], _at=at, **k: (calls.append((_m, a[_at])), _real(*a, **k))[1])
+    six = [jpegdec.L420, jpegdec.L444, jpegdec.GREY, jpegsamp.L422, jpegsamp.L440, jpegsamp.L411]
+    rs = np.random.RandomState(20)
+    for order in (rs.permutation(12), rs.permutation(24) % 12):
+        del calls[:]
+        out = jpegsamp.load_clip([files[k][1] for k in order])
+        assert out.shape == (len(order), 37, 53, 3) and out.dtype == torch.uint8
+        got = out.cpu().numpy()
+        for i, k in enumerate(order):
+            assert np.array_equal(got[i], want[k]), (i, k)
+        assert len(calls) == 12 and sorted(calls) == sorted([(m, l) for m in ('jpegdec', 'jpegprog') for l in six])

@@ -232,7 +232,8 @@ def test_c_entries_reject_bad_arguments_before_any_launch():
     assert lib.mg_jpegdec_limits(*[ctypes.byref(x) for x in v]) == 0 and lib.mg_jpegdec_limits(None, None, None, None, None) == -2
     assert [x.value for x in v] == [jpegdec.THREADS, jpegdec.MIN_SUB, jpegdec.MAX_SUB, jpegdec.DEFAULT_SUB, jpegdec.TAB_WORDS]
     header = open(os.path.join(ROOT, 'include', 'maggie_hip.h')).read()
-    for name, val in (('420', jpegdec.L420), ('444', jpegdec.L444), ('GREY', jpegdec.GREY), ('MAX_BYTES', '(1L << 28)')):
+    for name, val in (('420', jpegdec.L420), ('444', jpegdec.L444), ('GREY', jpegdec.GREY), ('422', jpegdec.L422), ('440', jpegdec.L440),
+                      ('411', jpegdec.L411), ('MAX_BYTES', '(1L << 28)')):
         assert '#define MG_JPEGDEC_%s %s\n' % (name, val) in header
     three = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
     a, b, c, odd = (ctypes.c_void_p(4096 * k) for k in (1, 2, 3, 4))
@@ -254,7 +255,7 @@ def test_c_entries_reject_bad_arguments_before_any_launch():
         return lib.mg_jpegdec_rgb(planes, L(pb), out, L(n), I(h), I(w), I(layout), I(e), mean, mean, None)
     assert sync(n=0) == coef(n=0, elems=0) == dcsum(n=0, elems=0) == idct(n=0, elems=0, pb=0) == rgb(n=0, pb=0) == 0
     assert sync(data=None) == coef(data=None) == dcsum(p=None) == idct(p=None) == rgb(planes=None) == -2
-    for bad in (dict(n=-1), dict(layout=3), dict(layout=-1)):
+    for bad in (dict(n=-1), dict(layout=6), dict(layout=-1)):
         assert sync(**bad) == coef(**bad) == dcsum(**bad) == idct(**bad) == rgb(**bad) == -2, bad
     for bad in (dict(nsub=0), dict(s=jpegdec.MIN_SUB - 1), dict(s=jpegdec.MAX_SUB + 1), dict(nsub=1 << 20, s=4096)):
         assert sync(**bad) == coef(**bad) == -2, bad

@@ -283,7 +283,7 @@ def test_c_entries_reject_bad_arguments_before_any_launch():
     def chains(n=1, h=16, w=16, layout=0, elems=6 * 64, nbytes=64, nscans=1, nchains=1, data=a, coef=d):
         return lib.mg_jpegprog_chains(data, L(nbytes), b, L(nscans), c, L(nchains), coef, L(elems), e, L(n), I(h), I(w), I(layout), None)
     assert chains(n=0, elems=0) == 0 and chains(nchains=0) == 0
-    for bad in (dict(n=-1), dict(layout=3), dict(layout=-1), dict(h=0), dict(w=0), dict(h=32768), dict(elems=6 * 64 - 1), dict(elems=12 * 64),
+    for bad in (dict(n=-1), dict(layout=6), dict(layout=-1), dict(h=0), dict(w=0), dict(h=32768), dict(elems=6 * 64 - 1), dict(elems=12 * 64),
                 dict(nbytes=-1), dict(nscans=-1), dict(nchains=-1), dict(data=None), dict(coef=None), dict(layout=1, elems=6 * 64)):
         assert chains(**bad) == -2, bad
 

@@ -1,6 +1,6 @@
 """Host side of the device decoder of the other chroma samplings (maggie_amd.utils.jpegsamp: 4:2:2, 4:4:0, 4:1:1): the restatement and its two
 writers against live Pillow on every case; `parse` on the list and on what it must refuse; argument errors before any launch; the dispatch of
-`load_clip`; the `_hv` C entries' argument errors; and the kernel sources themselves compiled for the host (one thread per GPU thread) under the
+`load_clip`; the C entries' argument errors at layouts 3, 4 and 5; and the kernel sources themselves compiled for the host (one thread per GPU thread) under the
 address and undefined-behaviour sanitizers as a stand-alone program, on the case list, at both epilogues, and on hostile streams. No GPU needed."""
 import ctypes
 import io
@@ -276,41 +276,47 @@ def test_load_dispatches_by_parsing_only(monkeypatch):
 
 
 # ---- the C entries ---------------------------------------------------------------------------------------------------------------------------------
-def test_hv_entries_reject_bad_arguments_before_any_launch():
+def test_pitched_layouts_reject_bad_arguments_before_any_launch():
     from maggie_amd import hip
     I, L = ctypes.c_int, ctypes.c_long
     lib = hip.lib()
-    for fn in (lib.mg_jpegdec_sync_hv, lib.mg_jpegdec_coef_hv, lib.mg_jpegdec_dcsum_hv, lib.mg_jpegdec_idct_hv, lib.mg_jpeg_rgb_hv,
-               lib.mg_jpegprog_chains_hv):
+    for fn in (lib.mg_jpegdec_sync, lib.mg_jpegdec_coef, lib.mg_jpegdec_dcsum, lib.mg_jpegdec_idct, lib.mg_jpeg_rgb_hv, lib.mg_jpegprog_chains):
         fn.restype = ctypes.c_int
     three = (ctypes.c_float * 3)(0.5, 0.5, 0.5)
     a, b, c = (ctypes.c_void_p(4096 * k) for k in (1, 2, 3))
     odd = ctypes.c_void_p(4100)
-    # 16 x 16 at (2, 1): one MCU column, two MCU rows, 4 blocks each; planes 16 x 16 + 2 x 16 x 8
+    L422, L440, L411 = jpegsamp.L422, jpegsamp.L440, jpegsamp.L411
+    assert (L422, L440, L411) == (3, 4, 5)
+    # 16 x 16 at 4:2:2: one MCU column, two MCU rows, 4 blocks each; planes 16 x 16 + 2 x 16 x 8
     E, PB = 8 * 64, 512
 
-    def sync(n=1, nsub=4, s=8, hv=(2, 1), launch=0, words=8, data=a, nbytes=64):
-        return lib.mg_jpegdec_sync_hv(data, L(nbytes), b, c, c, c, c, c, I(words), L(n), I(nsub), I(s), I(hv[0]), I(hv[1]), I(launch), None)
+    def sync(n=1, nsub=4, s=8, layout=L422, launch=0, words=8, data=a, nbytes=64):
+        return lib.mg_jpegdec_sync(data, L(nbytes), b, c, c, c, c, c, I(words), L(n), I(nsub), I(s), I(layout), I(launch), None)
 
-    def coef(n=1, nsub=4, s=8, h=16, w=16, hv=(2, 1), elems=E, data=a):
-        return lib.mg_jpegdec_coef_hv(data, L(64), b, c, c, c, c, L(elems), c, L(n), I(nsub), I(s), I(h), I(w), I(hv[0]), I(hv[1]), None)
+    def coef(n=1, nsub=4, s=8, h=16, w=16, layout=L422, elems=E, data=a):
+        return lib.mg_jpegdec_coef(data, L(64), b, c, c, c, c, L(elems), c, L(n), I(nsub), I(s), I(h), I(w), I(layout), None)
 
-    def dcsum(n=1, h=16, w=16, hv=(2, 1), elems=E, p=a):
-        return lib.mg_jpegdec_dcsum_hv(p, L(elems), b, L(n), I(h), I(w), I(hv[0]), I(hv[1]), None)
+    def dcsum(n=1, h=16, w=16, layout=L422, elems=E, p=a):
+        return lib.mg_jpegdec_dcsum(p, L(elems), b, L(n), I(h), I(w), I(layout), None)
 
-    def idct(n=1, h=16, w=16, hv=(2, 1), elems=E, pb=PB, planes=c, p=a):
-        return lib.mg_jpegdec_idct_hv(p, L(elems), b, planes, L(pb), L(n), I(h), I(w), I(hv[0]), I(hv[1]), None)
+    def idct(n=1, h=16, w=16, layout=L422, elems=E, pb=PB, planes=c, p=a):
+        return lib.mg_jpegdec_idct(p, L(elems), b, planes, L(pb), L(n), I(h), I(w), I(layout), None)
 
-    def rgb(n=1, h=16, w=16, hv=(2, 1), pb=PB, e=0, mean=three, planes=a, out=b):
-        return lib.mg_jpeg_rgb_hv(planes, L(pb), out, L(n), I(h), I(w), I(hv[0]), I(hv[1]), I(e), mean, mean, None)
+    def rgb(n=1, h=16, w=16, luma=(2, 1), pb=PB, e=0, mean=three, planes=a, out=b):
+        return lib.mg_jpeg_rgb_hv(planes, L(pb), out, L(n), I(h), I(w), I(luma[0]), I(luma[1]), I(e), mean, mean, None)
 
-    def chains(n=1, h=16, w=16, hv=(2, 1), elems=E, data=a, nbytes=64, nscans=1, nchains=1):
-        return lib.mg_jpegprog_chains_hv(data, L(nbytes), b, L(nscans), c, L(nchains), c, L(elems), c, L(n), I(h), I(w), I(hv[0]), I(hv[1]), None)
+    def chains(n=1, h=16, w=16, layout=L422, elems=E, data=a, nbytes=64, nscans=1, nchains=1):
+        return lib.mg_jpegprog_chains(data, L(nbytes), b, L(nscans), c, L(nchains), c, L(elems), c, L(n), I(h), I(w), I(layout), None)
     every = (sync, coef, dcsum, idct, rgb, chains)
+    layouts = (sync, coef, dcsum, idct, chains)
     assert sync(n=0) == coef(n=0, elems=0) == dcsum(n=0, elems=0) == idct(n=0, elems=0, pb=0) == rgb(n=0, pb=0) == chains(n=0, elems=0) == 0
     assert sync(data=None) == coef(data=None) == dcsum(p=None) == idct(p=None) == rgb(planes=None) == chains(data=None) == -2
-    for hv in ((2, 2), (1, 1), (3, 1), (0, 1), (1, 4), (2, 0), (4, 2), (-2, 1)):
-        assert [f(hv=hv) for f in every] == [-2] * 6, hv
+    for luma in ((2, 2), (1, 1), (3, 1), (0, 1), (1, 4), (2, 0), (4, 2), (-2, 1)):
+        assert rgb(luma=luma) == -2, luma
+    for layout in (6, 7, -1, 1 << 20):                                     # and the sizes of another layout's buffers do not fit this one's
+        assert [f(layout=layout) for f in layouts] == [-2] * 5, layout
+    for layout in (jpegdec.L420, jpegdec.L444, jpegdec.GREY, L411):
+        assert [f(layout=layout) for f in (coef, dcsum, idct, chains)] == [-2] * 4, layout
     assert [f(n=-1) for f in every] == [-2] * 6
     for bad in (dict(nsub=0), dict(s=jpegdec.MIN_SUB - 1), dict(s=jpegdec.MAX_SUB + 1), dict(nsub=1 << 20, s=4096)):
         assert sync(**bad) == coef(**bad) == -2, bad
@@ -321,12 +327,12 @@ def test_hv_entries_reject_bad_arguments_before_any_launch():
     assert idct(pb=PB - 1) == idct(pb=PB + 16) == idct(planes=odd) == idct(planes=None) == -2
     assert rgb(pb=PB - 1) == rgb(e=2) == rgb(e=-1) == rgb(mean=None) == rgb(out=a) == rgb(out=None) == rgb(planes=odd) == rgb(h=0) == rgb(w=32768) == -2
     # the pitched planes: 4:4:0 at w = 8 has luma and chroma rows of 16 bytes, 4:1:1 at w = 8 luma rows of 32 and chroma rows of 8
-    assert idct(hv=(1, 2), h=16, w=8, elems=4 * 64, pb=16 * 16 + 2 * 8 * 8) == rgb(hv=(1, 2), h=16, w=8, pb=16 * 16 + 2 * 8 * 8) == -2
-    assert idct(hv=(4, 1), h=8, w=8, elems=6 * 64, pb=8 * 8 * 3) == rgb(hv=(4, 1), h=8, w=8, pb=8 * 8 * 3) == -2
-    assert jpegdec.hv_geometry(16, 8, 1, 2) == (4, 16 * 16 + 2 * 8 * 16, 16, 16, 8, 16) and jpegdec.hv_geometry(8, 8, 4, 1) == (6, 8 * 32 + 2 * 8 * 8, 8, 32, 8, 8)
-    assert jpegdec.hv_geometry(16, 16, 2, 1)[:2] == (E // 64, PB)
+    assert idct(layout=L440, h=16, w=8, elems=4 * 64, pb=16 * 16 + 2 * 8 * 8) == rgb(luma=(1, 2), h=16, w=8, pb=16 * 16 + 2 * 8 * 8) == -2
+    assert idct(layout=L411, h=8, w=8, elems=6 * 64, pb=8 * 8 * 3) == rgb(luma=(4, 1), h=8, w=8, pb=8 * 8 * 3) == -2
+    assert jpegdec.geometry(16, 8, L440) == (4, 16 * 16 + 2 * 8 * 16, 16, 16, 8, 16) and jpegdec.geometry(8, 8, L411) == (6, 8 * 32 + 2 * 8 * 8, 8, 32, 8, 8)
+    assert jpegdec.geometry(16, 16, L422)[:2] == (E // 64, PB)
     header = open(os.path.join(ROOT, 'include', 'maggie_hip.h')).read()
-    for name in ('mg_jpegdec_sync_hv', 'mg_jpegdec_coef_hv', 'mg_jpegdec_dcsum_hv', 'mg_jpegdec_idct_hv', 'mg_jpeg_rgb_hv', 'mg_jpegprog_chains_hv'):
+    for name in ('mg_jpegdec_sync', 'mg_jpegdec_coef', 'mg_jpegdec_dcsum', 'mg_jpegdec_idct', 'mg_jpeg_rgb_hv', 'mg_jpegprog_chains'):
         assert 'int %s(' % name in header
 
 
@@ -334,7 +340,6 @@ def test_hv_entries_reject_bad_arguments_before_any_launch():
 def _case_bytes(datas, sub_bytes=8, recs=None):
     plans = [jpegsamp.parse(d) for d in datas]
     h, w, layout = plans[0].geometry
-    hs, vs = jpegsamp.LUMA[layout]
     T = len(datas)
     if plans[0].kind == 'baseline':
         offs = np.concatenate([[0], np.cumsum([len(d) for d in datas])])
@@ -345,7 +350,7 @@ def _case_bytes(datas, sub_bytes=8, recs=None):
         blob, scans, chains, qt = jpegprog.pack(plans, datas)
         recs = np.zeros((T, jpegdec.TAB_WORDS), np.int32)
         recs[:, 928:1120] = qt.reshape(T, 192)
-    head = struct.pack('<10i', plans[0].kind == 'progressive', h, w, hs, vs, sub_bytes, T, len(scans), len(chains), len(blob))
+    head = struct.pack('<10i', plans[0].kind == 'progressive', h, w, layout, 0, sub_bytes, T, len(scans), len(chains), len(blob))
     return head + recs.astype('<i4').tobytes() + scans.astype('<i4').tobytes() + chains.astype('<i4').tobytes() + blob
 
 
@@ -431,7 +436,7 @@ def test_host_build_stays_clean_on_hostile_streams(host_exe, tmp_path):
         scans[at, 457] //= 2
         recs = np.zeros((1, jpegdec.TAB_WORDS), np.int32)
         recs[:, 928:1120] = qt.reshape(1, 192)
-        cases.append(struct.pack('<10i', 1, 37, 53, 2, 1, 8, 1, len(scans), len(chains), len(data)) + recs.tobytes() + scans.astype('<i4').tobytes() +
+        cases.append(struct.pack('<10i', 1, 37, 53, jpegsamp.L422, 0, 8, 1, len(scans), len(chains), len(data)) + recs.tobytes() + scans.astype('<i4').tobytes() +
                      chains.astype('<i4').tobytes() + data)
         kinds.append('cut')
     for start, end in (('440_8x8_', 'qua100'), ('411_9x4_', 'prog_qua90'), ('422_4x4_', 'proT_qua50')):

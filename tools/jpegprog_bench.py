@@ -44,7 +44,7 @@ def chain_times(datas, reps):
     T = len(datas)
     blob = torch.frombuffer(bytearray(joined), dtype=torch.uint8).to(dev)
     d_scans = torch.from_numpy(scans).to(dev)
-    coef = torch.zeros((T, jpegdec.BLOCKS_PER_MCU[layout] * (-(-w // 16)) * (-(-h // 16)), 64), dtype=torch.int16, device=dev)
+    coef = torch.zeros((T, jpegdec.geometry(h, w, layout)[0], 64), dtype=torch.int16, device=dev)
     info = torch.zeros((T,), dtype=torch.int32, device=dev)
     # a chain's kind from its first scan record: Ss == 0 is the DC chain, else the AC chain of component word 464
     kind = np.where(scans[chains[:, 1], 459] == 0, -1, scans[chains[:, 1], 464])

@@ -1213,6 +1213,43 @@ int mg_pngdec_unfilter(const uint8_t* raw, long raw_stride, const int32_t* recs,
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * PNG frames and planes of every legal file (csrc/pngcolor.hip): the zlib streams of `files` files of one size -- any of the 15 (colour type,
+ * bit depth) pairs, Adam7 interlaced or not, per file -- -> Image.open(path).convert("RGB") or .convert("L") on the device. Replaces the frame
+ * half of T.Load for .png files (maggie/dataloader/transforms.py:47-50). DESIGN.md section 34. Grey 16 converts as min(v, 255) (Pillow's I;16),
+ * every other 16-bit sample as its high byte; alpha and tRNS are dropped.
+ *   recs    : int32 [files][MG_PNGCOLOR_REC_WORDS]: [0] the offset of the zlib stream in `data`, [1] its length, [2] colour type, [3] bit depth,
+ *             [4] palette entries (256 without a palette), [5] interlace (0 / 1), [6] the inflated size: the sum over the non-empty passes of
+ *             ph x (1 + rb), [7] 0, [_REC_PASSES + 4 k ..] pass k (7 for Adam7, else 1; the rest zero): pw, ph, rb, byte offset in the file's `raw`
+ *             slice, with pw = ceil((w - x0) / dx), ph = ceil((h - y0) / dy), rb = ceil(pw x channels x depth / 8) (the kernels recompute the
+ *             table and refuse a record that differs), [_REC_LTABLE ..] the L of each palette entry as 256 bytes, [_REC_PALETTE ..] 256 x 3
+ *             palette bytes.
+ *   raw     : uint8 [files][raw_stride] as for mg_pngdec_*; mg_pngcolor_unfilter reconstructs the scanlines IN PLACE (filter type bytes stay).
+ *   info    : int32 [files][MG_PNGDEC_INFO_WORDS], zeroed by the caller; the words and the MG_PNGDEC_ST_* bits of mg_pngdec_*.
+ *   mg_pngcolor_inflate  : mg_pngdec_inflate's algorithm (csrc/png_inflate.h), expecting recs[6] bytes.
+ *   mg_pngcolor_unfilter : one wave per (file, pass); a filter type above 4 sets MG_PNGDEC_ST_FILTER and decodes as type 0.
+ *   mg_pngcolor_convert  : raw -> out, `mode` _OUT_RGB uint8 [files][h][w][3], _OUT_L uint8 [files][h][w] (`out` at any byte), _OUT_NORM float32
+ *             [files][3][h][w] = (v / 255 - mean[c]) / std[c] with IEEE divisions (`mean`, `std`: 3 host floats; `out` 4-byte aligned). Skips a
+ *             file whose status is not 0; a palette index past the last entry sets MG_PNGDEC_ST_INDEX.
+ * Each returns -2 for an argument error (before any launch; a destination overlapping `raw` is one), -3 when the launch would exceed a grid
+ * dimension. Every access is bounded by `data_bytes`, `raw_stride` and h, w; a record that does not fit them sets MG_PNGDEC_ST_RECORD.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_PNGCOLOR_REC_WORDS 292
+#define MG_PNGCOLOR_REC_PASSES 8
+#define MG_PNGCOLOR_REC_LTABLE 36
+#define MG_PNGCOLOR_REC_PALETTE 100
+#define MG_PNGCOLOR_MAX_ROWBYTES 32768 /* RGBA 16 at 3840 pixels is 30720; the carry row of a band stays in LDS */
+#define MG_PNGCOLOR_GROUP 16           /* pixels of a lane of mg_pngcolor_convert */
+#define MG_PNGCOLOR_OUT_RGB 0
+#define MG_PNGCOLOR_OUT_L 1
+#define MG_PNGCOLOR_OUT_NORM 2
+int mg_pngcolor_limits(int* threads, int* max_side, int* max_rowbytes, int* rec_words, int* info_words, int* group);
+int mg_pngcolor_inflate(const uint8_t* data, long data_bytes, const int32_t* recs, uint8_t* raw, long raw_stride, int32_t* info, long files, int h,
+                        int w, void* stream);
+int mg_pngcolor_unfilter(uint8_t* raw, long raw_stride, const int32_t* recs, int32_t* info, long files, int h, int w, void* stream);
+int mg_pngcolor_convert(const uint8_t* raw, long raw_stride, const int32_t* recs, void* out, int32_t* info, long files, int h, int w, int mode,
+                        const float* mean, const float* std, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
  * PNG encoding (csrc/pngenc.hip): `nplanes` planes of one size [nplanes][h][w] -> the zlib streams (78 01, deflate, Adler-32) of 8-bit
  * greyscale, non-interlaced PNG files, Sub filter on every row, packed back to back. Replaces the pixel pass of the result writer
  * (maggie/engine/test.py:20-68). The host adds the signature, IHDR, the IDAT length and CRC, and IEND. DESIGN.md section 27.

@@ -6,6 +6,7 @@ on the host. `geometry.resize_short_pad(jpegdec.decode_clip(...), pngdec.decode_
                      concatenated into one zlib stream, and that stream's two header bytes. Raises `Unsupported` (the class of
                      `jpegdec.Unsupported`, a ValueError) for what the device does not decode -- Adam7, 16-bit samples, sides above
                      `mg_pngdec_limits` -- so that a loader's single `except` falls back to PIL, and a plain ValueError for a broken file.
+  * `walk`           `parse` under a caller's acceptance rules: what `pngcolor.parse` runs with its own (16-bit samples, Adam7, wider rows).
   * `decode`         one file -> uint8 (h, w) on the device.
   * `decode_planes`  P files of one size (colour type and depth may differ per file) -> (P, h, w) from ONE set of launches.
   * `decode_stats`   the same, returning the inflated bytes, the status words and the counters: for the tests and tools/pngdec_bench.py.
@@ -63,9 +64,27 @@ def luma(rgb):
     return ((19595 * c[..., 0] + 38470 * c[..., 1] + 7471 * c[..., 2] + 0x8000) >> 16).astype(np.uint8)
 
 
+def _accepts(w, h, depth, ct, lace):
+    """What this module decodes of the legal files: raises `Unsupported` by name, else returns the inflated size."""
+    if lace:
+        raise Unsupported('Adam7 interlace')
+    if depth == 16:
+        raise Unsupported('16-bit samples')
+    if w > MAX_SIDE or h > MAX_SIDE or rowbytes(ct, depth, w) > MAX_ROWBYTES or h * (1 + rowbytes(ct, depth, w)) > MAX_RAW - 16:
+        raise Unsupported('%d x %d at %d bytes a row: sides up to %d and rows up to %d bytes are decoded'
+                          % (w, h, rowbytes(ct, depth, w), MAX_SIDE, MAX_ROWBYTES))
+    return h * (1 + rowbytes(ct, depth, w))
+
+
 def parse(data):
     """The chunk walk of one file's bytes -> PngPlan. Host only. `Unsupported` for Adam7, 16-bit samples and sides above the limits;
     ValueError for a bad signature, a bad CRC of a critical chunk, a truncated file, a missing IHDR, IDAT or PLTE, a bad zlib header."""
+    return walk(data, _accepts)
+
+
+def walk(data, accepts):
+    """`parse` under a module's own rules (this one's and `pngcolor`'s): `accepts(w, h, depth, ct, interlace)` raises `Unsupported` for a legal
+    file the module does not decode and returns the inflated size. The plan carries `interlace` too."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError('data must be the bytes of a PNG file (got %s)' % type(data).__name__)
     d = bytes(data)
@@ -109,13 +128,7 @@ def parse(data):
     w, h, depth, ct, comp, filt, lace = ihdr
     if ct not in DEPTHS or depth not in DEPTHS[ct] or comp != 0 or filt != 0 or lace > 1 or w < 1 or h < 1:
         raise ValueError('a malformed IHDR chunk (%d x %d, colour type %d, depth %d, methods %d %d %d)' % (w, h, ct, depth, comp, filt, lace))
-    if lace:
-        raise Unsupported('Adam7 interlace')
-    if depth == 16:
-        raise Unsupported('16-bit samples')
-    if w > MAX_SIDE or h > MAX_SIDE or rowbytes(ct, depth, w) > MAX_ROWBYTES or h * (1 + rowbytes(ct, depth, w)) > MAX_RAW - 16:
-        raise Unsupported('%d x %d at %d bytes a row: sides up to %d and rows up to %d bytes are decoded'
-                          % (w, h, rowbytes(ct, depth, w), MAX_SIDE, MAX_ROWBYTES))
+    raw_size = accepts(w, h, depth, ct, lace)
     if not idat:
         raise ValueError('no IDAT chunk')
     if not ended:
@@ -136,13 +149,13 @@ def parse(data):
         ltable[:entries] = luma(palette)
     else:
         entries = 256
-        if ct == 0:
+        if ct == 0 and depth <= 8:
             ltable[:1 << depth] = np.arange(1 << depth) * (255 // ((1 << depth) - 1))
         else:
             ltable[:] = np.arange(256)
     rb = rowbytes(ct, depth, w)
     return PngPlan(width=w, height=h, depth=depth, color_type=ct, palette=palette if ct == 3 else None, stream=stream, idat_chunks=len(idat),
-                   rowbytes=rb, raw_size=h * (1 + rb), ltable=ltable, entries=entries)
+                   rowbytes=rb, raw_size=raw_size, ltable=ltable, entries=entries, interlace=lace)
 
 
 def record(plan, offset):

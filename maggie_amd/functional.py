@@ -1905,7 +1905,8 @@ class DtSSD(torch.autograd.Function):
     def backward(ctx, gout):
         p, g, m, sums = ctx.saved_tensors
         pbs, gbs, mbs, B, T, E, sig, shape = ctx.meta
-        dp = torch.empty(shape, dtype=torch.float32, device=p.device)
+        # a one-frame slice has no frame pair: mg_dtssd_bwd launches nothing, the gradient is zero (loss_dtSSD on it: NaN loss, zero gradient)
+        dp = (torch.zeros if T < 2 else torch.empty)(shape, dtype=torch.float32, device=p.device)
         K.hip.call('mg_dtssd_bwd', K.hip.ptr(p), K.c_long(pbs), K.hip.ptr(g), K.c_long(gbs), K.hip.ptr(m), K.c_long(mbs), K.c_int(B), K.c_int(T),
                    K.c_long(E), K.c_int(sig), K.hip.ptr(sums), K.hip.ptr(gout.float().contiguous().view(1)), K.hip.ptr(dp), K.c_long(T * E), K.hip.stream())
         return dp, None, None, None

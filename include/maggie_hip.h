@@ -1389,6 +1389,46 @@ int mg_bg_compose(const uint8_t* fg, const uint8_t* alpha, const uint8_t* bg, lo
                   const double* wt, uint8_t* out, uint8_t* fg_out, uint8_t* bg_out, void* stream);
 int mg_bg_limits(int* max_ksize, int* win_table, int* tile_rows, int* tile_cols, int* max_side);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Colour PNG encoding (csrc/pngenc.hip): `nimages` images of one size [nimages][h][w][channels] uint8, channels 3 (colour type 2) or 4
+ * (colour type 6) -> the zlib streams of 8-bit non-interlaced files, Sub filter on every row with the filter distance `channels`. Only the
+ * filtered stream differs from the grey entries: a row is 01 and channels x w bytes, byte j of it minus byte j - channels (j >= channels).
+ * Blocks, records, sizes, the blob and the return codes are those of mg_pngenc_size / mg_pngenc_emit with a row of channels x w bytes:
+ * channels x w <= MG_PNGENC_MAX_WIDTH and h x (1 + channels x w) <= MG_PNGENC_MAX_RAW. DESIGN.md section 35.
+ * ------------------------------------------------------------------------------------------------------------- */
+int mg_pngenc_size_rgb(const uint8_t* images, int channels, long nimages, int h, int w, int32_t* recs, int64_t* sizes, void* stream);
+int mg_pngenc_emit_rgb(const uint8_t* images, int channels, long nimages, int h, int w, const int32_t* recs, const int64_t* sizes, uint8_t* out,
+                       long out_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Cut-outs (csrc/cutout.hip): the foreground colour of every instance by the blur-fusion estimator (Forte & Pitie, ICIP 2021) stated on
+ * bytes, two passes with the radii r0 then r1, and the straight RGBA image. DESIGN.md section 35 is the statement. The file is compiled
+ * without floating-point contraction; nothing reads back or synchronises and the launches form one chain, so a call can be captured in a graph.
+ *   mg_cutout_alpha_bytes : fp32 [n] (4-byte aligned) -> uint8 [n], byte = (uint8)(x * 255.0f), NaN and x < 0 -> 0, x >= 1 -> 255
+ *             (MG_PNGENC_MODE_UNIT).
+ *   mg_cutout_estimate : frames_u8 [frames][H][W][3], alpha_u8 [frames * P][H][W] -> out uint8 [frames * P][H][W][out_channels]:
+ *             out_channels 3 the estimate F, 4 (out 4-byte aligned) the cut-out (F, a) with F = 0 where a == 0. One pass P(I, F, B, a, r):
+ *             window [y - r/2, y - r/2 + r) x [x - r/2, x - r/2 + r), indices reflected without repeating the edge (period 2 (n - 1),
+ *             as often as needed); SA = sum a, SFA = sum F a, SBA = sum B (255 - a), exact integers < 2^32; then in fp64, every
+ *             operation rounded on its own: ba = SA / (255 r r), bF = (SFA / (65025 r r)) / (ba + 1e-5),
+ *             bB = (SBA / (65025 r r)) / ((1 - ba) + 1e-5), al = a / 255, i = I / 255, f = bF + al ((i - al bF) - (1 - al) bB);
+ *             F' = floor(clip(f, 0, 1) 255 + 0.5), B' = floor(clip(bB, 0, 1) 255 + 0.5). The estimate is F1, B1 = P(I, I, I, a, r0),
+ *             F = P(I, F1, B1, a, r1). Scratch, all caller-owned, for `chunk` >= 1 planes at a time: rows uint32 [chunk][7][H][W]
+ *             (4-byte aligned), f1 and b1 uint8 [chunk][H][W][3]. 4 launches per chunk.
+ * Each returns -2 for an argument error before any launch (a null pointer, a side outside 1..MG_CUTOUT_MAX_SIDE, a radius outside
+ * 1..MG_CUTOUT_MAX_RADIUS, a channel count, a misaligned base).
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_CUTOUT_THREADS 256
+#define MG_CUTOUT_TILE 256               /* columns of a row-sum workgroup: 2 x 7 x (256 + 254) uint32 of LDS, 28 560 bytes */
+#define MG_CUTOUT_GROUP 8                /* neighbours added first when a window has 16 taps or more */
+#define MG_CUTOUT_STRIP 32               /* rows a column lane walks down; twice as many for windows of 32 rows and more */
+#define MG_CUTOUT_MAX_RADIUS 255
+#define MG_CUTOUT_MAX_SIDE 32767
+int mg_cutout_limits(int* threads, int* tile, int* strip, int* max_radius, int* max_side);
+int mg_cutout_alpha_bytes(const float* alpha, long n, uint8_t* out, void* stream);
+int mg_cutout_estimate(const uint8_t* frames_u8, const uint8_t* alpha_u8, long frames, int P, int H, int W, int r0, int r1, uint32_t* rows,
+                       uint8_t* f1, uint8_t* b1, long chunk, uint8_t* out, int out_channels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,8 @@
 //   (maggie/engine/test.py:20-68: `(alphas * 255).astype('uint8')`, `> 0.5`, cv2.imwrite). The signature, IHDR, the IDAT length and CRC and
 //   IEND are the host's (maggie_amd/utils/pngenc.py); DESIGN.md section 27 holds the algorithm, the LDS table and the measurements;
 //   tests/pngenc_restatement.py states the same encoder sequentially and is its byte-for-byte oracle.
+//   The colour entries (mg_pngenc_size_rgb / mg_pngenc_emit_rgb: RGB and RGBA images) run the same kernels on rows of
+//   channels x w bytes with the filter distance `channels`; only pe_load_block knows the difference.
 //
 // The filtered stream of a plane (h x (1 + w) bytes: 01, p[0], p[1] - p[0], ...) is cut into deflate blocks of MG_PNGENC_BLOCK_BYTES; one
 //   workgroup of MG_PNGENC_THREADS lanes handles one block, lane t the bytes [64 t, 64 t + 64). Tokens are runs only (distance 1) and never
@@ -91,8 +93,9 @@ __device__ __forceinline__ int pe_pixel(const void* __restrict__ src, int mode, 
     return !(y >= 0.f) ? 0 : (y >= 255.f ? 255 : (int)y);                  // NaN and negatives -> 0
 }
 
-// the bytes [k PB, k PB + n) of the plane's filtered stream -> fb
-__device__ __forceinline__ void pe_load_block(const void* __restrict__ src, int mode, long plane, int h, int w, int k, int n, uint8_t* fb, int tid) {
+// the bytes [k PB, k PB + n) of the plane's filtered stream -> fb. `w` is the BYTES of a row and `bpp` the filter distance: 1 for a grey
+// plane, the channel count (and w = channels x width) for a colour image, whose samples are uint8
+__device__ __forceinline__ void pe_load_block(const void* __restrict__ src, int mode, long plane, int h, int w, int bpp, int k, int n, uint8_t* fb, int tid) {
     const unsigned pitch = (unsigned)w + 1u;
     const long base = plane * (long)h * w;
     for (int i = tid; i < n; i += PT) {
@@ -102,7 +105,7 @@ __device__ __forceinline__ void pe_load_block(const void* __restrict__ src, int 
         if (c >= 1) {
             const long at = base + (long)r * w + (c - 1);
             v = pe_pixel(src, mode, at);
-            if (c >= 2) v = (v - pe_pixel(src, mode, at - 1)) & 255;
+            if (c > (unsigned)bpp) v = (v - pe_pixel(src, mode, at - bpp)) & 255;
         }
         fb[i] = (uint8_t)v;
     }
@@ -282,7 +285,7 @@ __device__ __forceinline__ void pe_put(uint32_t* img, int bit, uint32_t v, int n
 __device__ __forceinline__ int pe_blocks(int h, int w) { return (int)(((long)h * (w + 1) + PB - 1) / PB); }
 
 __global__ void __launch_bounds__(MG_PNGENC_THREADS)
-pe_size_kernel(const void* __restrict__ src, int mode, int h, int w, int32_t* __restrict__ recs) {
+pe_size_kernel(const void* __restrict__ src, int mode, int h, int w, int bpp, int32_t* __restrict__ recs) {
     __shared__ __attribute__((aligned(16))) uint8_t fb[PB];
     __shared__ int hist[288], clhist[20], wt[4], ntok;
     __shared__ unsigned long long acc[2];
@@ -301,7 +304,7 @@ pe_size_kernel(const void* __restrict__ src, int mode, int h, int w, int32_t* __
     if (tid < 20) { clhist[tid] = 0; cllens[tid] = 0; }
     if (tid < 2) acc[tid] = 0;
     if (tid == 0) ntok = 0;
-    pe_load_block(src, mode, plane, h, w, k, n, fb, tid);
+    pe_load_block(src, mode, plane, h, w, bpp, k, n, fb, tid);
     const Span sp = pe_spans(fb, n, tid, wt);
     unsigned long long s1 = 0, s2 = 0;
     for (int i = sp.a; i < sp.e; ++i) { const unsigned b = fb[i]; s1 += b; s2 += (unsigned long long)b * (unsigned)(n - i); }
@@ -365,7 +368,7 @@ pe_total_kernel(const int32_t* __restrict__ recs, int h, int w, int64_t* __restr
 }
 
 __global__ void __launch_bounds__(MG_PNGENC_THREADS)
-pe_emit_kernel(const void* __restrict__ src, int mode, int h, int w, const int32_t* __restrict__ recs, const int64_t* __restrict__ sizes,
+pe_emit_kernel(const void* __restrict__ src, int mode, int h, int w, int bpp, const int32_t* __restrict__ recs, const int64_t* __restrict__ sizes,
                uint8_t* __restrict__ out, long out_bytes) {
     __shared__ __attribute__((aligned(16))) uint8_t fb[PB];
     __shared__ __attribute__((aligned(16))) uint32_t img[IMG_WORDS];
@@ -397,7 +400,7 @@ pe_emit_kernel(const void* __restrict__ src, int mode, int h, int w, const int32
     if (tid < 5) *reinterpret_cast<uint32_t*>(cllens + 4 * tid) = (uint32_t)rec[80 + tid] & 0x07070707u;
     if (tid < 4) acc[tid] = 0;
     for (int i = tid; i < IMG_WORDS; i += PT) img[i] = 0;
-    pe_load_block(src, mode, plane, h, w, k, n, fb, tid);
+    pe_load_block(src, mode, plane, h, w, bpp, k, n, fb, tid);
     // the bytes of the planes in front, the bits of this plane's blocks in front, and (the last block) the Adler-32 of the plane
     unsigned long long off = 0, pre = 0, a1 = 0, a2 = 0;
     for (long q = tid; q < plane; q += PT) off += (unsigned long long)sizes[q];
@@ -512,24 +515,48 @@ extern "C" int mg_pngenc_limits(int* threads, int* block_bytes, int* rec_words, 
     return 0;
 }
 
-extern "C" int mg_pngenc_size(const void* planes, int mode, long nplanes, int h, int w, int32_t* recs, int64_t* sizes, void* stream) {
+// the launches of both forms: `w` the bytes of a row, `bpp` the filter distance
+static int pe_size_launch(const void* planes, int mode, long nplanes, int h, int w, int bpp, int32_t* recs, int64_t* sizes, void* stream) {
     if (pe_bad_args(planes, mode, nplanes, h, w) || !recs || !sizes || (uintptr_t)recs % 4 != 0 || (uintptr_t)sizes % 8 != 0) return -2;
     const long grid = nplanes * (((long)h * (w + 1) + PB - 1) / PB);
     if (grid > 0x7fffffffL) return -3;
-    hipLaunchKernelGGL(pe_size_kernel, dim3((unsigned)grid), dim3(PT), 0, (hipStream_t)stream, planes, mode, h, w, recs);
+    hipLaunchKernelGGL(pe_size_kernel, dim3((unsigned)grid), dim3(PT), 0, (hipStream_t)stream, planes, mode, h, w, bpp, recs);
     MG_CHECK_LAUNCH();
     hipLaunchKernelGGL(pe_total_kernel, dim3((unsigned)nplanes), dim3(PT), 0, (hipStream_t)stream, (const int32_t*)recs, h, w, sizes);
     MG_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int mg_pngenc_emit(const void* planes, int mode, long nplanes, int h, int w, const int32_t* recs, const int64_t* sizes, uint8_t* out,
-                              long out_bytes, void* stream) {
+static int pe_emit_launch(const void* planes, int mode, long nplanes, int h, int w, int bpp, const int32_t* recs, const int64_t* sizes, uint8_t* out,
+                          long out_bytes, void* stream) {
     if (pe_bad_args(planes, mode, nplanes, h, w) || !recs || !sizes || !out || (uintptr_t)recs % 4 != 0 || (uintptr_t)sizes % 8 != 0) return -2;
     if ((uintptr_t)out % 16 != 0 || out_bytes < 8 || out_bytes % 4 != 0) return -2;
     const long grid = nplanes * (((long)h * (w + 1) + PB - 1) / PB);
     if (grid > 0x7fffffffL) return -3;
-    hipLaunchKernelGGL(pe_emit_kernel, dim3((unsigned)grid), dim3(PT), 0, (hipStream_t)stream, planes, mode, h, w, recs, sizes, out, out_bytes);
+    hipLaunchKernelGGL(pe_emit_kernel, dim3((unsigned)grid), dim3(PT), 0, (hipStream_t)stream, planes, mode, h, w, bpp, recs, sizes, out, out_bytes);
     MG_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int mg_pngenc_size(const void* planes, int mode, long nplanes, int h, int w, int32_t* recs, int64_t* sizes, void* stream) {
+    return pe_size_launch(planes, mode, nplanes, h, w, 1, recs, sizes, stream);
+}
+
+extern "C" int mg_pngenc_emit(const void* planes, int mode, long nplanes, int h, int w, const int32_t* recs, const int64_t* sizes, uint8_t* out,
+                              long out_bytes, void* stream) {
+    return pe_emit_launch(planes, mode, nplanes, h, w, 1, recs, sizes, out, out_bytes, stream);
+}
+
+// colour: [nimages][h][w][channels] uint8 is [nimages][h][channels w] bytes with the filter distance `channels`
+static inline int pe_bad_colour(int channels, int w) { return (channels != 3 && channels != 4) || w < 1 || w > MG_PNGENC_MAX_WIDTH / channels; }
+
+extern "C" int mg_pngenc_size_rgb(const uint8_t* images, int channels, long nimages, int h, int w, int32_t* recs, int64_t* sizes, void* stream) {
+    if (pe_bad_colour(channels, w)) return -2;
+    return pe_size_launch(images, MG_PNGENC_MODE_U8, nimages, h, channels * w, channels, recs, sizes, stream);
+}
+
+extern "C" int mg_pngenc_emit_rgb(const uint8_t* images, int channels, long nimages, int h, int w, const int32_t* recs, const int64_t* sizes,
+                                  uint8_t* out, long out_bytes, void* stream) {
+    if (pe_bad_colour(channels, w)) return -2;
+    return pe_emit_launch(images, MG_PNGENC_MODE_U8, nimages, h, channels * w, channels, recs, sizes, out, out_bytes, stream);
 }

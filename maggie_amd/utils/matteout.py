@@ -7,7 +7,7 @@ instance planes, and the files. The fp32 planes never cross to the host and need
                        and faster as measured, as `reverse_transform_tensor` in front of it.
   * `overlay`          `Image.blend(image, palette(mask > 0), alpha)` (app.py:59-65).
   * `label_planes`     `np.unique` of a label map and `(map == id) * 255` per id (maggie_predictor.py:35-40).
-  * `predict_image`    maggie_predictor.py:52-78 with any callable model: `predict_item` -> model -> composites.
+  * `predict_image`    maggie_predictor.py:52-78 with any callable model: `predict_item` -> model -> composites (and, asked for, cut-outs).
   * `save_composites`, `save_overlay`   the .jpg files (maggie_predictor.py:158-162, app.py:67-71) through one `jpegenc.encode_clip`.
   * `VideoMatteWriter` the body of the video predictor's loop (maggie_predictor.py:121-167).
 
@@ -194,12 +194,14 @@ def label_planes(label_map, *, device=None):
     return ids, planes
 
 
-def predict_image(model, frame_u8, instances, *, preprocessor=None, background=GREEN, postprocess=False):
+def predict_image(model, frame_u8, instances, *, preprocessor=None, background=GREEN, postprocess=False, cutouts=False):
     """maggie_predictor.py:52-78 on the device: `frame_u8` (H, W, 3) uint8 and `instances`, a label map (H, W) or uint8 planes (n, H, W) of
     0 / 255 -> {'alpha': (n, H, W) fp32, 'composites': (n, H, W, 3) uint8}. `model` is any callable with the model's contract
     (batch -> {'refined_masks': (1, 1, n, Hp, Wp)}); it runs under `no_grad`. `preprocessor`: a `preprocess.DevicePreprocessor` (default: a
     new one). The alpha is reverse-transformed, snapped and composited by `composite(transform_info=..., snap=True)`; with `postprocess` it is
-    reverse-transformed and snapped, filtered by `postprocessing.postprocess` (the largest component, as the video predictor does at :130) and composited at full size."""
+    reverse-transformed and snapped, filtered by `postprocessing.postprocess` (the largest component, as the video predictor does at :130) and composited at full size.
+    With `cutouts` the result also has 'cutouts': (n, H, W, 4) uint8, `cutout.cutout` of the frame and the returned alpha (straight RGBA with
+    an estimated foreground colour instead of the frame's own: utils/cutout.py)."""
     from .preprocess import DevicePreprocessor
     frame = check_u8(frame_u8, 'frame')
     if frame.dim() != 3 or frame.shape[-1] != 3:
@@ -219,16 +221,24 @@ def predict_image(model, frame_u8, instances, *, preprocessor=None, background=G
     dev = resolve_device(pre.device, planes if planes.is_cuda else frame)
     n = int(planes.shape[0])
     if n == 0:
-        return {'alpha': torch.empty((0, H, W), dtype=torch.float32, device=dev), 'composites': torch.empty((0, H, W, 3), dtype=torch.uint8, device=dev)}
+        empty = {'alpha': torch.empty((0, H, W), dtype=torch.float32, device=dev), 'composites': torch.empty((0, H, W, 3), dtype=torch.uint8, device=dev)}
+        if cutouts:
+            empty['cutouts'] = torch.empty((0, H, W, 4), dtype=torch.uint8, device=dev)
+        return empty
     frame = to_device(frame, dev)
     batch, info = pre.predict_item(frame, planes)
     with torch.no_grad():
         pred = model(batch)['refined_masks']
     if postprocess:
         alpha = postprocessing.postprocess(postprocessing.reverse_transform_tensor(pred, info, snap=True)).reshape(n, H, W)
-        return {'alpha': alpha, 'composites': composite(frame, alpha, background)[0]}
-    comp, alpha = composite(frame, pred.float(), background, transform_info=info, snap=True, return_alpha=True)
-    return {'alpha': alpha[0], 'composites': comp[0]}
+        out = {'alpha': alpha, 'composites': composite(frame, alpha, background)[0]}
+    else:
+        comp, alpha = composite(frame, pred.float(), background, transform_info=info, snap=True, return_alpha=True)
+        out = {'alpha': alpha[0], 'composites': comp[0]}
+    if cutouts:
+        from . import cutout as _cutout                        # (that module imports this one)
+        out['cutouts'] = _cutout.cutout(frame, out['alpha'])[0]
+    return out
 
 
 def _write_all(paths, files):

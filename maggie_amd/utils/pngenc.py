@@ -6,6 +6,10 @@ stay on the device; what comes back to the host is the compressed stream, tens o
   * `encode`              one plane (h, w) -> bytes.
   * `encode_stats`        the same, returning the block records, the stream sizes, the blob and the guard slices: for the tests and
                           tools/pngenc_bench.py.
+  * `encode_images`       N colour images of one size (N, h, w, C), C = 3 (RGB, colour type 2) or 4 (RGBA, colour type 6) -> N complete
+                          PNG files, the writer of `cutout.save_cutouts`; `encode_image` one image, `encode_images_stats` the `Encoded` record.
+                          Only the filtered stream differs (Sub with the filter distance C); tokens, Huffman codes, emit and Adler-32 are
+                          the grey path's.
   * `save_visualization`  the reference's signature, directory and file-name rule; `functools.partial(save_visualization, save_dir=...)` is
                           the `callback` of `eval_image` / `eval_video`.
 
@@ -40,9 +44,13 @@ SIGNATURE = b'\x89PNG\r\n\x1a\n'
 IEND = struct.pack('>I', 0) + b'IEND' + struct.pack('>I', zlib.crc32(b'IEND'))
 
 
-def frame(h, w, stream):
-    """The PNG file around one zlib stream: signature, IHDR (8-bit greyscale, non-interlaced), one IDAT, IEND. Host only."""
-    ihdr = b'IHDR' + struct.pack('>IIBBBBB', w, h, 8, 0, 0, 0, 0)
+COLOUR_TYPE = {1: 0, 3: 2, 4: 6}                              # channels -> the IHDR colour type
+
+
+def frame(h, w, stream, channels=1):
+    """The PNG file around one zlib stream: signature, IHDR (8-bit, greyscale or for 3 / 4 channels RGB / RGBA, non-interlaced), one IDAT,
+    IEND. Host only."""
+    ihdr = b'IHDR' + struct.pack('>IIBBBBB', w, h, 8, COLOUR_TYPE[channels], 0, 0, 0)
     idat = b'IDAT' + bytes(stream)
     return b''.join((SIGNATURE, struct.pack('>I', 13), ihdr, struct.pack('>I', zlib.crc32(ihdr)),
                      struct.pack('>I', len(idat) - 4), idat, struct.pack('>I', zlib.crc32(idat)), IEND))
@@ -93,11 +101,16 @@ def _guarded(nbytes, guard, dev, fill=None):
 
 
 def run(x, mode, *, guard=0, stats=False):
-    """The launches themselves: `x` a contiguous device tensor (P, h, w) of the mode's type. `guard`: bytes of 0xA5 kept on both sides of
-    the record table, the size table and the blob. Returns an `Encoded`."""
+    """The launches themselves: `x` a contiguous device tensor (P, h, w) of the mode's type, or uint8 (N, h, w, C) with C = 3 or 4 (the colour
+    entries). `guard`: bytes of 0xA5 kept on both sides of the record table, the size table and the blob. Returns an `Encoded`."""
     hip.need_cuda(x)
-    P, h, w = x.shape
-    nb = blocks_of(h, w)
+    channels = int(x.shape[3]) if x.dim() == 4 else 1
+    P, h, w = (int(v) for v in x.shape[:3])
+    nb = blocks_of(h, channels * w)
+    if channels == 1:
+        size_entry, emit_entry, form = 'mg_pngenc_size', 'mg_pngenc_emit', c_int(MODES[mode])
+    else:
+        size_entry, emit_entry, form = 'mg_pngenc_size_rgb', 'mg_pngenc_emit_rgb', c_int(channels)
     dev = x.device
     guard = -(-guard // 16) * 16
     with torch.cuda.device(dev):
@@ -105,19 +118,19 @@ def run(x, mode, *, guard=0, stats=False):
         size_b, g2 = _guarded(-(-(P * 8) // 16) * 16, guard, dev)
         recs, sizes = rec_b.view(torch.int32), size_b.view(torch.int64)
         st = hip.stream
-        hip.call('mg_pngenc_size', hip.ptr(x), c_int(MODES[mode]), c_long(P), c_int(h), c_int(w), hip.ptr(recs), hip.ptr(sizes), st())
+        hip.call(size_entry, hip.ptr(x), form, c_long(P), c_int(h), c_int(w), hip.ptr(recs), hip.ptr(sizes), st())
         host_sizes = sizes[:P].cpu().numpy()                                   # read-back 1
         total = int(host_sizes.sum())
         padded = max(-(-total // 4) * 4, 8)
         blob, g3 = _guarded(padded, guard, dev, fill=0)
-        hip.call('mg_pngenc_emit', hip.ptr(x), c_int(MODES[mode]), c_long(P), c_int(h), c_int(w), hip.ptr(recs), hip.ptr(sizes), hip.ptr(blob),
+        hip.call(emit_entry, hip.ptr(x), form, c_long(P), c_int(h), c_int(w), hip.ptr(recs), hip.ptr(sizes), hip.ptr(blob),
                  c_long(padded), st())
         data = blob[:total].cpu().numpy().tobytes()                            # read-back 2: exactly the bytes
     r = Encoded()
     ends = np.cumsum(host_sizes)
     r.sizes, r.readbacks = host_sizes, 2
     r.streams = [data[int(e - s):int(e)] for s, e in zip(host_sizes, ends)]
-    r.files = [frame(h, w, s) for s in r.streams]
+    r.files = [frame(h, w, s, channels) for s in r.streams]
     if stats:
         r.recs = recs[:P * nb * REC_WORDS].cpu().numpy().reshape(P, nb, REC_WORDS)
         r.blob, r.slack, r.guards = blob[:total], blob[total:], g1 + g2 + g3
@@ -150,6 +163,58 @@ def encode_stats(planes, *, mode='u8', device=None, guard=0):
     """`encode_planes` returning the whole `Encoded` record (block records, sizes, blob, guard slices): for the tests and
     tools/pngenc_bench.py. One more read-back (the records) than `encode_planes`."""
     return _encode(planes, mode, device, guard=guard, stats=True)
+
+
+def _check_images(images):
+    """Type and shape checks of the colour form, before anything touches the device -> the tensor (an array becomes a host tensor)."""
+    if isinstance(images, np.ndarray):
+        images = torch.from_numpy(np.ascontiguousarray(images))
+    if not torch.is_tensor(images):
+        raise TypeError('images must be a tensor or an array (got %s)' % type(images).__name__)
+    if images.dtype != torch.uint8:
+        raise TypeError('colour images are uint8 (got %s)' % images.dtype)
+    if images.dim() != 4 or images.shape[3] not in (3, 4):
+        raise ValueError('images must be (N, h, w, 3) or (N, h, w, 4) (got %s)' % (tuple(images.shape),))
+    N, h, w, C = (int(v) for v in images.shape)
+    if not 1 <= N <= MAX_PLANES:
+        raise ValueError('1..%d images a call (got %d)' % (MAX_PLANES, N))
+    if not 1 <= h <= MAX_SIDE or not 1 <= w <= MAX_WIDTH // C or h * (C * w + 1) > MAX_RAW:
+        raise ValueError('heights of 1..%d and, with %d channels, widths of 1..%d are written (got %d x %d)' % (MAX_SIDE, C, MAX_WIDTH // C, h, w))
+    if N * blocks_of(h, C * w) > 0x7fffffff:
+        raise ValueError('%d images of %d x %d are more deflate blocks than one launch takes' % (N, h, w))
+    return images
+
+
+def _encode_images(images, device, guard=0, stats=False):
+    x = _check_images(images)
+    need_gpu(x)
+    x = x.to(resolve_device(device, x), non_blocking=True).contiguous()
+    return run(x, 'u8', guard=guard, stats=stats)
+
+
+def encode_images(images_u8, *, device=None):
+    """N colour images of one size, uint8 (N, h, w, C) with C = 3 (RGB) or 4 (straight RGBA), a device tensor (an array or a host tensor is
+    uploaded) -> a list of N bytes objects, each a complete PNG file of colour type 2 / 6: 8-bit, non-interlaced, one IDAT, Sub filter on every
+    row with the filter distance C, the grey path's deflate. A row of the filtered stream is 1 + C * w bytes, and `MAX_WIDTH` (16384) bounds
+    the BYTES of a row in the grey path (a grey row is w bytes; `pngdec` reads back rows of at most MAX_ROWBYTES = 16384 bytes), so a colour
+    row is held to the same C * w <= 16384: w <= 5461 for RGB and w <= 4096 for RGBA, h <= 32767, h * (C * w + 1) <= MAX_RAW
+    (`pngcolor.decode_frames` reads all of these back). TypeError for another dtype,
+    ValueError for a wrong shape or a size beyond these, both before any launch. One `mg_pngenc_size_rgb` and one `mg_pngenc_emit_rgb`, two
+    read-backs. Not graph-capturable."""
+    return _encode_images(images_u8, device).files
+
+
+def encode_image(image_u8, *, device=None):
+    """One image (h, w, 3) or (h, w, 4) -> the bytes of its PNG file."""
+    if not (torch.is_tensor(image_u8) or isinstance(image_u8, np.ndarray)) or image_u8.ndim != 3:
+        raise ValueError('image must be a tensor or an array of shape (h, w, 3) or (h, w, 4)')
+    return _encode_images(image_u8[None], device).files[0]
+
+
+def encode_images_stats(images_u8, *, device=None, guard=0):
+    """`encode_images` returning the whole `Encoded` record (block records, sizes, blob, guard slices): for the tests and
+    tools/cutout_bench.py. One more read-back (the records) than `encode_images`."""
+    return _encode_images(images_u8, device, guard=guard, stats=True)
 
 
 def _png_name(name):

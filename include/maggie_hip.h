@@ -1429,6 +1429,54 @@ int mg_cutout_alpha_bytes(const float* alpha, long n, uint8_t* out, void* stream
 int mg_cutout_estimate(const uint8_t* frames_u8, const uint8_t* alpha_u8, long frames, int P, int H, int W, int r0, int r1, uint32_t* rows,
                        uint8_t* f1, uint8_t* b1, long chunk, uint8_t* out, int out_channels, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Full-size mattes (csrc/refine.hip): the fast guided filter (He & Sun) stated on bytes. A local linear model alpha ~ a . I + b is fitted at
+ * the network's size and its averaged coefficients, brought to full size bilinearly, are applied to the full-size frame. DESIGN.md section 36
+ * is the statement, tests/refine_restatement.py the same arithmetic in NumPy and the byte-for-byte oracle. The file is compiled without
+ * floating-point contraction and uses no fp32 between the sums and the bytes; nothing reads back or synchronises and the launches of an entry
+ * form one chain, so both entries can be captured in a graph. No equality with a float implementation is claimed.
+ *   Inputs per frame: I uint8 [H][W][3] (full size), the guide G uint8 [h][w][3] (the frame as the network saw it), per instance p uint8 [h][w].
+ *   Parameters: window side r, 1..MG_REFINE_MAX_RADIUS, n = r r; eps, MG_REFINE_MIN_EPS..1, in units of the squared [0, 1] range.
+ *   1. Window [y - r/2, y - r/2 + r) x [x - r/2, x - r/2 + r) (integer division), indices reflected without repeating the edge (period
+ *      2 (len - 1), as often as needed; an axis of length 1 maps everything to 0).
+ *   2. Window sums, exact integers < 2^32: per frame SI_c (3) and SII_cd, c <= d (6), of G_c G_d; per instance Sp and SIp_c (3) of G_c p.
+ *   3. Per low-resolution pixel in fp64, every operation rounded on its own, in this order:
+ *      m_c = SI_c / (255.0 n), mp = Sp / (255.0 n); s_cd = SII_cd / (65025.0 n) - m_c m_d, then s_cc = s_cc + eps;
+ *      k_c = SIp_c / (65025.0 n) - m_c mp;
+ *      c00 = s11 s22 - s12 s12, c01 = s02 s12 - s01 s22, c02 = s01 s12 - s02 s11, c11 = s00 s22 - s02 s02, c12 = s01 s02 - s00 s12,
+ *      c22 = s00 s11 - s01 s01; det = (s00 c00 + s01 c01) + s02 c02;
+ *      a_0 = ((c00 k_0 + c01 k_1) + c02 k_2) / det, a_1 with the row (c01, c11, c12), a_2 with the row (c02, c12, c22);
+ *      b = mp - ((a_0 m_0 + a_1 m_1) + a_2 m_2);
+ *      A_c = floor(clip(a_c, -256, 256) 65536.0 + 0.5), B = floor(clip(b, -1024, 1024) 65536.0 + 0.5), integers (16 fractional bits).
+ *      The model gives |a| <= 0.25 / sqrt(eps) <= 250 for eps >= 1e-6 and |b| <= 1 + 3 |a|: the two clips are guards that never act.
+ *   4. The same window over A_c and B: exact integer sums, |sum| < 2^39; abar_c = (double)sum A_c / (n 65536.0), bbar likewise, one division each.
+ *   5. To full size. Along x: ratio = w / W (fp64), s = (X + 0.5) ratio - 0.5 clamped to [0, w - 1], x0 = floor(s), x1 = min(x0 + 1, w - 1),
+ *      fx = s - x0; the y axis likewise with h / H. For a plane v: top = v[y0][x0] (1 - fx) + v[y0][x1] fx, bot likewise on row y1,
+ *      up(v) = top (1 - fy) + bot fy. q = ((up(bbar) + up(abar_0) i_0) + up(abar_1) i_1) + up(abar_2) i_2 with i_c = I_c / 255.0;
+ *      byte = floor(clip(q, 0, 1) 255.0 + 0.5); with snap a byte <= 1 becomes 0 and a byte >= 254 becomes 255.
+ *   mg_refine_coefficients : guide [frames][h][w][3], alpha_u8 [frames * P][h][w] -> means fp64 [frames * P][4][h][w] = (abar_0, abar_1,
+ *             abar_2, bbar), steps 1-4. Scratch, all caller-owned: grows and gsums uint32 [frames][9][h][w] (planes SI_0..2, SII_00, 01, 02,
+ *             11, 12, 22; 4-byte aligned), prows uint32 [frames * P][4][h][w], coef int32 [frames * P][4][h][w] (A_0..2, B), crows int64
+ *             [frames * P][4][h][w] and means (8-byte aligned). 6 launches.
+ *   mg_refine_apply : frames_u8 [frames][H][W][3], means -> out uint8 [frames * P][H][W] and/or outf fp32 [frames * P][H][W] = byte / 255.0f
+ *             (either may be null, not both), step 5 in one launch: a lane owns MG_REFINE_LANE_PIXELS consecutive pixels of one row, loads
+ *             their frame bytes once and loops over the frame's instances. xi int32 [W] / xf fp64 [W] hold x0 / fx, yi [H] / yf [H] hold
+ *             y0 / fy (made on the host in fp64; an index outside the plane is clamped into it by the kernel).
+ * Each returns -2 for an argument error before any launch (a null pointer, a side outside 1..MG_CUTOUT_MAX_SIDE, a side of the window outside
+ * 1..MG_REFINE_MAX_RADIUS, an eps outside MG_REFINE_MIN_EPS..1, a misaligned base); frames * P == 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------------------------- */
+#define MG_REFINE_THREADS 256
+#define MG_REFINE_TILE 256               /* columns of a row-sum workgroup: 9 x (256 + 63) uint32 of LDS, 11 484 bytes */
+#define MG_REFINE_STRIP 32               /* rows a column lane walks down */
+#define MG_REFINE_MAX_RADIUS 64
+#define MG_REFINE_LANE_PIXELS 4
+#define MG_REFINE_MIN_EPS 1e-6
+int mg_refine_limits(int* threads, int* tile, int* strip, int* max_radius, int* max_side, int* lane_pixels);
+int mg_refine_coefficients(const uint8_t* guide_u8, const uint8_t* alpha_u8, long frames, int P, int h, int w, int r, double eps, uint32_t* grows,
+                           uint32_t* gsums, uint32_t* prows, int32_t* coef, int64_t* crows, double* means, void* stream);
+int mg_refine_apply(const uint8_t* frames_u8, const double* means, long frames, int P, int h, int w, int H, int W, const int32_t* xi,
+                    const double* xf, const int32_t* yi, const double* yf, int snap, uint8_t* out, float* outf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

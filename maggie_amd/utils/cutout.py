@@ -6,7 +6,8 @@ and written with the matte as a straight (not premultiplied) RGBA image.
   * `estimate_foreground`  the blur-fusion estimator (Forte & Pitie, "Approximate Fast Foreground Colour Estimation", ICIP 2021), applied
                            twice with the radii 90 and 6, per instance.
   * `cutout`               RGBA: the estimate, the alpha byte, RGB 0 where the alpha byte is 0; with `transform_info` the alpha goes through
-                           `postprocessing.reverse_transform_tensor` first, as `composite`'s default form does.
+                           `postprocessing.reverse_transform_tensor` first, as `composite`'s default form does, or with `refine=` through
+                           the guided filter of utils/refine.py.
   * `save_cutouts`         `out_dir/NN_<stem>.png` through one `pngenc.encode_images`.
 
 The estimator is STATED ON BYTES (tests/cutout_restatement.py is the statement in NumPy and the byte-for-byte oracle): the
@@ -25,6 +26,7 @@ import torch
 from .. import hip
 from ..hip import c_int, c_long
 from . import postprocessing
+from . import refine as _refine
 from ._inputs import check_u8, integer, need_gpu, to_device
 from .matteout import _frames
 
@@ -102,10 +104,18 @@ def estimate_foreground(frames_u8, alpha, *, radii=RADII, device=None):
     return _run(f, alpha, T, P, H, W, r, 3, device)
 
 
-def cutout(frames_u8, alpha, *, transform_info=None, snap=False, radii=RADII, device=None):
+def cutout(frames_u8, alpha, *, transform_info=None, snap=False, radii=RADII, refine=False, device=None):
     """Straight RGBA cut-outs, uint8 (T, P, H, W, 4): A is the alpha byte, RGB the estimate of `estimate_foreground`, and RGB is 0 where A is 0
     (hidden colour is useless and costs file size). With `transform_info` (the loader's list) the float32 alpha is at the network's size and
-    first goes through `postprocessing.reverse_transform_tensor(alpha, transform_info, snap=snap)`. Errors and capture as `estimate_foreground`."""
+    first goes through `postprocessing.reverse_transform_tensor(alpha, transform_info, snap=snap)`. With `refine` (True, or a dict with `radius`
+    and / or `eps`) the alpha bytes are those of `refine.refine(frames_u8, alpha, transform_info=transform_info, snap=snap, ...)` instead: the
+    guided filter against the full-size frame in place of the bilinear reverse transform. Errors and capture as `estimate_foreground`."""
+    opts = _refine.options(refine)
+    if opts is not None:
+        r = _radii(radii)
+        a8 = _refine.refine(frames_u8, alpha, transform_info=transform_info, snap=snap, device=device, **opts)
+        T, P, H, W = (int(v) for v in a8.shape)
+        return _run(_frames(frames_u8)[0], a8, T, P, H, W, r, 4, device)
     f, T, H, W, P, r = _checked(frames_u8, alpha, radii, transform_info)
     if transform_info is not None and T * P:
         need_gpu(alpha)

@@ -194,15 +194,20 @@ def label_planes(label_map, *, device=None):
     return ids, planes
 
 
-def predict_image(model, frame_u8, instances, *, preprocessor=None, background=GREEN, postprocess=False, cutouts=False):
+def predict_image(model, frame_u8, instances, *, preprocessor=None, background=GREEN, postprocess=False, cutouts=False, refine=False):
     """maggie_predictor.py:52-78 on the device: `frame_u8` (H, W, 3) uint8 and `instances`, a label map (H, W) or uint8 planes (n, H, W) of
     0 / 255 -> {'alpha': (n, H, W) fp32, 'composites': (n, H, W, 3) uint8}. `model` is any callable with the model's contract
     (batch -> {'refined_masks': (1, 1, n, Hp, Wp)}); it runs under `no_grad`. `preprocessor`: a `preprocess.DevicePreprocessor` (default: a
     new one). The alpha is reverse-transformed, snapped and composited by `composite(transform_info=..., snap=True)`; with `postprocess` it is
     reverse-transformed and snapped, filtered by `postprocessing.postprocess` (the largest component, as the video predictor does at :130) and composited at full size.
     With `cutouts` the result also has 'cutouts': (n, H, W, 4) uint8, `cutout.cutout` of the frame and the returned alpha (straight RGBA with
-    an estimated foreground colour instead of the frame's own: utils/cutout.py)."""
+    an estimated foreground colour instead of the frame's own: utils/cutout.py). With `refine` (True, or a dict with `radius` and / or `eps`) the
+    alpha is `refine.refine(frame, prediction, transform_info=..., snap=True, as_float=True)`, the guided filter against the full-size frame
+    (utils/refine.py), in place of the bilinear reverse transform: byte / 255, so the composites and the cut-outs are made from the refined
+    bytes; with `postprocess` the largest-component filter runs on it."""
     from .preprocess import DevicePreprocessor
+    from . import refine as _refine                          # (that module imports this one)
+    ropts = _refine.options(refine)
     frame = check_u8(frame_u8, 'frame')
     if frame.dim() != 3 or frame.shape[-1] != 3:
         raise ValueError('frame must be (H, W, 3) (got shape %s)' % (tuple(frame.shape),))
@@ -229,7 +234,12 @@ def predict_image(model, frame_u8, instances, *, preprocessor=None, background=G
     batch, info = pre.predict_item(frame, planes)
     with torch.no_grad():
         pred = model(batch)['refined_masks']
-    if postprocess:
+    if ropts is not None:
+        alpha = _refine.refine(frame, pred.float(), transform_info=info, snap=True, as_float=True, **ropts).reshape(n, H, W)
+        if postprocess:
+            alpha = postprocessing.postprocess(alpha)
+        out = {'alpha': alpha, 'composites': composite(frame, alpha, background)[0]}
+    elif postprocess:
         alpha = postprocessing.postprocess(postprocessing.reverse_transform_tensor(pred, info, snap=True)).reshape(n, H, W)
         out = {'alpha': alpha, 'composites': composite(frame, alpha, background)[0]}
     else:
